@@ -17,8 +17,22 @@ the scan kernel of other rule-set shapes, and for the dense 1-byte-key sets
 (rx, short, fuzz0, fuzz3) their verified-only step (verified_step_ms: scan,
 result and pre-verification on the host's clock).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set-up, the clock
+warm-up, W warm-up steps, the K timed steps, and the line with the value,
+ms_per_step, the roofline of the timed steps' own kernel events and, for N > 1,
+their per-rank attribution.  --full adds every other leg, each switched off
+by its own flag as before: the other rule sets (--no-other), the verified
+step, the pre-verification cost, the golden check of the last step's
+candidates (--no-check) and the CPU baselines (--no-cpu); without --full
+those fields of the line are null.  --dump-outputs DIR writes what the last
+timed step returned (rank 0), for comparing two builds output for output:
+DIR/positions.npy, the ascending candidate positions as float64 (exact below
+2^53; a fixed seeded sample of DUMP_MAX_POSITIONS of them if there are more),
+and DIR/count.npy, their number.  The input is generated from --seed, so the
+same arguments give the same input on every run.
 
 With --gpus N > 1 and no launcher around it (WORLD_SIZE unset) bench.py starts
 the N rank processes itself, before anything touches the GPU, with torchrun's
@@ -51,6 +65,7 @@ sys.path.insert(0, REPO)
 
 GiB = 1 << 30
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md)
+DUMP_MAX_POSITIONS = 4 << 20   # --dump-outputs: 32 MiB of float64
 
 
 def parse():
@@ -62,6 +77,11 @@ def parse():
     ap.add_argument("--gib-per-gpu", type=float, default=4.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--cpu-sample-mib", type=int, default=3072)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: other rule sets, verified "
+                         "step, pre-verification cost, golden check, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's candidate positions to DIR/*.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-other", action="store_true",
@@ -320,6 +340,21 @@ def load_traffic(kernel_bytes):
     return None, "profiles/pmc_traffic.json is for another input size"
 
 
+def dump_outputs(d, positions):
+    """--dump-outputs: the last timed step's ascending candidate positions and
+    their number as float64 .npy files; beyond DUMP_MAX_POSITIONS positions,
+    the ones at a fixed (seeded) ascending choice of indices."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = positions.size
+    if n > DUMP_MAX_POSITIONS:
+        idx = np.random.default_rng(0).choice(n, DUMP_MAX_POSITIONS, replace=False)
+        idx.sort()
+        positions = positions[idx]
+    np.save(os.path.join(d, "positions.npy"), positions.astype(np.float64))
+    np.save(os.path.join(d, "count.npy"), np.array([n], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -443,14 +478,14 @@ def main():
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
-    # Order of the legs: the secondary measurements first (the other rule sets'
+    # Order of the legs (--full): the secondary measurements first (the other rule sets'
     # kernel times, the verification-complete step), the headline last.
     # the same input under the other rule sets of SURVEY.md §8d (kernel time only,
     # not the bench value): B = 1,000 4-byte hex atoms, E = 2,000 nocase/masked;
     # and the shapes with 1-byte keys, whose candidates are dense:
     # rx = regexps, short = short literals, fuzz0 / fuzz3 = generated rule sets
     other = None
-    if rank == 0 and world == 1 and not args.no_other and args.rules == "C":
+    if args.full and rank == 0 and world == 1 and not args.no_other and args.rules == "C":
         other = {}
         for name in ("B", "E", "rx", "short", "fuzz0", "fuzz3"):
             t_o = yara_amd.Tables.from_npz(os.path.join(REPO, "tests", "golden", "tables",
@@ -513,30 +548,36 @@ def main():
         if use_dist:
             return ydist.gather_rows(ydist.records_to_rows(ptr, n_rec, dev))
         return n_rec
-    for _ in range(max(args.warmup, 3)):
-        verified_step()
-    if use_dist:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        v_out = verified_step()
-    torch.cuda.synchronize()
-    if use_dist:
-        dist.barrier()
-    v_elapsed = time.perf_counter() - t0
-    if use_dist:
-        t = torch.tensor([v_elapsed], dtype=torch.float64,
-                         device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        v_elapsed = float(t.item())
-    verified = {"ms_per_step": round(v_elapsed / args.steps * 1e3, 4),
+
+    def time_verified_step():
+        for _ in range(max(args.warmup, 3)):
+            verified_step()
+        if use_dist:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            v_out = verified_step()
+        torch.cuda.synchronize()
+        if use_dist:
+            dist.barrier()
+        v_elapsed = time.perf_counter() - t0
+        if use_dist:
+            t = torch.tensor([v_elapsed], dtype=torch.float64,
+                             device=dev if args.backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            v_elapsed = float(t.item())
+        return {"ms_per_step": round(v_elapsed / args.steps * 1e3, 4),
                 "value": round(total * args.steps / v_elapsed / 1e9, 3), "unit": "GB/s",
                 "records": int(v_out if not use_dist else (v_out.shape[0] if v_out is not None else -1)),
                 "what": "scan + compaction + on-device pre-verification (yr_amd_verify_device)"
                         + ("" if not use_dist else " of each rank's window + %s gather of the "
                            "{offset, pool index} records to rank 0"
                            % ("RCCL" if args.backend == "nccl" else args.backend))}
+
+    verified = time_verified_step() if args.full else None
+
+    # the headline: W warm-up steps, then the K timed steps
 
     run(args.warmup)
     for sc in scanners:
@@ -589,13 +630,26 @@ def main():
     k_avg = sum(kernel_ms) / len(kernel_ms)
     achieved = shard / (k_avg * 1e-3) / 1e9
 
+    # what the last timed step returned, on the host (rank 0): the ascending
+    # candidate positions of the whole block
+    p = None
+    if rank == 0 and (args.dump_outputs or (args.full and not args.no_check)):
+        if not use_dist:
+            ptr, cnt = pos
+            pos = torch.empty(max(cnt, 1), dtype=torch.int64, device=dev)
+            memcpy(pos.data_ptr(), ptr, cnt * 8, 3)
+            pos = pos[:cnt]
+        p = pos.cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, p)
+
     # parity spot check of this run's own output (rank 0): ascending and the
     # candidate count of config C at 4 GiB recorded from the reference run
     # on-device pre-verification of the last step's candidates (SURVEY.md §8f
     # rows 1 and 4; not part of the timed step): how many of the reference's
     # verify calls can have an effect, and what it costs on the GPU
     preverify = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         scanner.scan_device(buf.data_ptr(), total)
         scanner.device_result()
         torch.cuda.synchronize()
@@ -608,13 +662,7 @@ def main():
                              "synchronous, wall clock)"}
 
     check = None
-    if rank == 0 and not args.no_check:
-        if not use_dist:
-            ptr, cnt = pos
-            pos = torch.empty(max(cnt, 1), dtype=torch.int64, device=dev)
-            memcpy(pos.data_ptr(), ptr, cnt * 8, 3)
-            pos = pos[:cnt]
-        p = pos.cpu().numpy()
+    if args.full and rank == 0 and not args.no_check:
         ok = bool((p[1:] > p[:-1]).all()) if p.size > 1 else True
         check = {"ascending": ok, "candidates": int(p.size)}
         if args.rules == "C" and shard == 4 * GiB and args.seed == 1 and world <= 8:
@@ -635,7 +683,7 @@ def main():
     if rank == 0:
         traffic, traffic_src = load_traffic(shard)
         cpu = cpu1 = cpu_par = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             import oracle
             sample = oracle.xorshift(args.cpu_sample_mib << 20, args.seed)
             info = cpu_info()
@@ -676,6 +724,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -695,7 +744,8 @@ def main():
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic,
                          "traffic_source": traffic_src,
-                         "kernel": "scan_segments_kernel", "kernel_ms_avg": round(k_avg, 4)},
+                         "kernel": "scan_segments_kernel", "kernel_ms_avg": round(k_avg, 4),
+                         "kernel_launches": len(kernel_ms)},
             "cpu_baseline": cpu,
             "cpu_baseline_1thread": cpu1,
             "cpu_port_parallel": cpu_par,

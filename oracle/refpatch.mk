@@ -8,8 +8,8 @@
 #
 # Outputs (git-ignored; travel to the GPU box):
 #   oracle/_ref/libyara_patched.so          stock libyara + the patch
-#   integration/_build/libyara_gpu_hook.so  yr_gpu_scanner.c -DYR_HAVE_BLOCK_SCANNER
-#   integration/_build/e2e_check_hook       e2e_check.c -DE2E_BLOCK_SCANNER: the GPU
+#   oracle/_ref/libyara_gpu_hook.so  yr_gpu_scanner.c -DYR_HAVE_BLOCK_SCANNER
+#   oracle/_ref/e2e_check_hook       e2e_check.c -DE2E_BLOCK_SCANNER: the GPU
 #                                           side through libyara's own entry points
 REF ?= /root/reference
 MAKEFLAGS += -r
@@ -36,8 +36,8 @@ OTHER := proc/linux tlshc/tlsh tlshc/tlsh_impl tlshc/tlsh_util
 SRCS := $(CORE) $(MODS) $(OTHER)
 OBJS := $(patsubst %,$(OBJ)/%.o,$(subst /,_,$(SRCS))) $(OBJ)/scanner.o
 
-all: $(OUT)/libyara_patched.so integration/_build/libyara_gpu_hook.so \
-     integration/_build/e2e_check_hook
+all: $(OUT)/libyara_patched.so $(OUT)/libyara_gpu_hook.so \
+     $(OUT)/e2e_check_hook
 
 $(SCRATCH)/.stamp: $(PATCH) oracle/refpatch.mk
 	rm -rf $(SCRATCH)
@@ -68,17 +68,15 @@ $(OUT)/libyara_patched.so: $(OBJS)
 	$(CC) -shared -o $@ $(OBJS) -lpthread -lm
 
 HOOK_LIBS := -L$(OUT) -lyara_patched -Lyara_amd -lyara_amd \
-             -Wl,-rpath,'$$ORIGIN/../../oracle/_ref' -Wl,-rpath,'$$ORIGIN/../../yara_amd' \
-             -Wl,-rpath,'$$ORIGIN'
+             -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../yara_amd'
 
-integration/_build/libyara_gpu_hook.so: integration/yr_gpu_scanner.c integration/yr_gpu_scanner.h \
+$(OUT)/libyara_gpu_hook.so: integration/yr_gpu_scanner.c integration/yr_gpu_scanner.h \
                                         $(OUT)/libyara_patched.so include/yara_amd.h
-	@mkdir -p integration/_build
 	$(CC) -O2 -D_GNU_SOURCE -Wall -Wno-unused-function -fPIC -DYR_HAVE_BLOCK_SCANNER $(INC) \
 	  -shared -o $@ integration/yr_gpu_scanner.c $(HOOK_LIBS)
 
-integration/_build/e2e_check_hook: integration/e2e_check.c integration/_build/libyara_gpu_hook.so
+$(OUT)/e2e_check_hook: integration/e2e_check.c $(OUT)/libyara_gpu_hook.so
 	$(CC) -O2 -D_GNU_SOURCE -Wall -Wno-unused-function -DYR_HAVE_BLOCK_SCANNER -DE2E_BLOCK_SCANNER \
-	  $(INC) -o $@ integration/e2e_check.c -Lintegration/_build -lyara_gpu_hook $(HOOK_LIBS) -lpthread -lm
+	  $(INC) -o $@ integration/e2e_check.c -lyara_gpu_hook $(HOOK_LIBS) -lpthread -lm
 
 .PHONY: all

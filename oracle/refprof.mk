@@ -9,8 +9,8 @@
 #
 # Outputs (git-ignored; travel to the GPU box):
 #   oracle/_ref/libyara_prof.so              stock libyara, -DYR_PROFILING_ENABLED
-#   integration/_build/libyara_gpu_prof.so   yr_gpu_scanner.c, same define
-#   integration/_build/e2e_check_prof        e2e_check.c, same define
+#   oracle/_ref/libyara_gpu_prof.so   yr_gpu_scanner.c, same define
+#   oracle/_ref/e2e_check_prof        e2e_check.c, same define
 REF ?= /root/reference
 MAKEFLAGS += -r
 .SUFFIXES:
@@ -34,8 +34,8 @@ OTHER := proc/linux tlshc/tlsh tlshc/tlsh_impl tlshc/tlsh_util
 SRCS := $(CORE) $(MODS) $(OTHER)
 OBJS := $(patsubst %,$(OBJ)/%.o,$(subst /,_,$(SRCS)))
 
-all: $(OUT)/libyara_prof.so integration/_build/libyara_gpu_prof.so \
-     integration/_build/e2e_check_prof
+all: $(OUT)/libyara_prof.so $(OUT)/libyara_gpu_prof.so \
+     $(OUT)/e2e_check_prof
 
 define OBJ_RULE
 $(OBJ)/$(subst /,_,$(1)).o: $(REF)/libyara/$(1).c
@@ -48,16 +48,14 @@ $(OUT)/libyara_prof.so: $(OBJS)
 	$(CC) -shared -o $@ $(OBJS) -lpthread -lm
 
 PROF_LIBS := -L$(OUT) -lyara_prof -Lyara_amd -lyara_amd \
-             -Wl,-rpath,'$$ORIGIN/../../oracle/_ref' -Wl,-rpath,'$$ORIGIN/../../yara_amd' \
-             -Wl,-rpath,'$$ORIGIN'
+             -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../yara_amd'
 
-integration/_build/libyara_gpu_prof.so: integration/yr_gpu_scanner.c integration/yr_gpu_scanner.h \
+$(OUT)/libyara_gpu_prof.so: integration/yr_gpu_scanner.c integration/yr_gpu_scanner.h \
                                         $(OUT)/libyara_prof.so include/yara_amd.h
-	@mkdir -p integration/_build
 	$(CC) -O2 -D_GNU_SOURCE -Wall -Wno-unused-function -fPIC $(DEFS) $(INC) \
 	  -shared -o $@ integration/yr_gpu_scanner.c $(PROF_LIBS)
 
-integration/_build/e2e_check_prof: integration/e2e_check.c integration/_build/libyara_gpu_prof.so
+$(OUT)/e2e_check_prof: integration/e2e_check.c $(OUT)/libyara_gpu_prof.so
 	$(CC) -O2 -D_GNU_SOURCE -Wall -Wno-unused-function $(DEFS) $(INC) -o $@ integration/e2e_check.c \
-	  -Lintegration/_build -lyara_gpu_prof $(PROF_LIBS) -lpthread -lm
+	  -lyara_gpu_prof $(PROF_LIBS) -lpthread -lm
 .PHONY: all

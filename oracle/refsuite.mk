@@ -11,8 +11,9 @@
 #                 the suites as upstream runs them (CPU, pins the fixtures)
 #   <suite>-gpu   the same sources with every scan entry point renamed at
 #                 compile time (REDIRECT) into integration/refsuite_gpu.c, which
-#                 scans through the GPU integration (integration/_build/
-#                 libyara_gpu_shim.so -> yara_amd/libyara_amd.so)
+#                 scans through the GPU integration (integration/
+#                 Makefile: oracle/_ref/libyara_gpu_shim.so ->
+#                 yara_amd/libyara_amd.so)
 #
 #   make -f oracle/refsuite.mk REF=/root/reference
 #
@@ -46,9 +47,11 @@ REDIRECT := -Dyr_rules_scan_mem=ygt_rules_scan_mem \
             -Dyr_scanner_destroy=ygt_scanner_destroy
 
 REFLIB := -Loracle/_ref -lyara_ref -Wl,-rpath,'$$ORIGIN/..'
-GPULIB := -Lintegration/_build -lyara_gpu_shim -Loracle/_ref -lyara_ref -Lyara_amd -lyara_amd \
-          -Wl,-rpath,'$$ORIGIN/../../../integration/_build' -Wl,-rpath,'$$ORIGIN/..' \
-          -Wl,-rpath,'$$ORIGIN/../../../yara_amd'
+# the -gpu suites load the shim that integration/Makefile builds into
+# oracle/_ref/, beside libyara_ref.so: one folder ($ORIGIN/..) holds both
+SHIM := oracle/_ref/libyara_gpu_shim.so
+GPULIB := -Loracle/_ref -lyara_gpu_shim -lyara_ref -Lyara_amd -lyara_amd \
+          -Wl,-rpath,'$$ORIGIN/..' -Wl,-rpath,'$$ORIGIN/../../../yara_amd'
 
 SUITES := test-rules test-async test-api
 
@@ -63,8 +66,8 @@ $(OUT)/%: $(REF)/tests/%.c $(REF)/tests/util.c oracle/_ref/libyara_ref.so | $(OU
 $(OUT)/refsuite_gpu.o: integration/refsuite_gpu.c integration/yr_gpu_scanner.h | $(OUT)
 	$(CC) -O2 -D_GNU_SOURCE -Wall -I$(REF)/libyara/include -I$(REF)/libyara -c $< -o $@
 
-$(OUT)/%-gpu: $(REF)/tests/%.c $(REF)/tests/util.c $(OUT)/refsuite_gpu.o \
-              integration/_build/libyara_gpu_shim.so | $(OUT)
+$(OUT)/%-gpu: $(REF)/tests/%.c $(REF)/tests/util.c $(OUT)/refsuite_gpu.o $(SHIM) \
+              oracle/refsuite.mk | $(OUT)
 	$(CC) $(CFLAGS_T) $(REDIRECT) $(REF)/tests/$*.c $(REF)/tests/util.c $(OUT)/refsuite_gpu.o \
 	  -o $@ $(GPULIB) -lpthread -lm
 

@@ -6,7 +6,9 @@ CPU tests: the rank environments (--launch-only), the real spawn path with
 children that report their environment and exit before importing torch
 (--rank-probe), and that one failing rank ends the others and sets the exit
 code.  GPU test: two gloo ranks on the box's one GPU run the whole bench and
-print an n_gpus = 2 line whose candidates match config D's stock goldens.
+print an n_gpus = 2 line whose candidates match config D's stock goldens
+(`--full`: the golden check is a leg beside the headline).  A plain run times
+its steps only and `--dump-outputs` writes the last step's candidates.
 """
 import json
 import os
@@ -92,12 +94,41 @@ def test_world_size_mismatch_is_an_error():
     assert "WORLD_SIZE=2" in r.stderr
 
 
+def test_dump_outputs_samples_a_long_position_list_reproducibly(tmp_path):
+    # more positions than DUMP_MAX_POSITIONS: a fixed ascending sample of them
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    n = bench.DUMP_MAX_POSITIONS + 12345
+    positions = np.arange(n, dtype=np.int64) * 3 + 7
+    outs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        bench.dump_outputs(d, positions)
+        assert sorted(os.listdir(d)) == ["count.npy", "positions.npy"]
+        assert np.load(os.path.join(d, "count.npy")).tolist() == [float(n)]
+        outs.append(np.load(os.path.join(d, "positions.npy")))
+    a, b = outs
+    assert a.dtype == np.float64 and a.size == bench.DUMP_MAX_POSITIONS
+    assert a.nbytes + 8 <= 64 * 10**6
+    assert np.array_equal(a, b)
+    assert (a[1:] > a[:-1]).all()
+    idx = (a.astype(np.int64) - 7) // 3
+    assert np.array_equal(positions[idx].astype(np.float64), a)      # all taken from the list
+    assert idx[-1] > bench.DUMP_MAX_POSITIONS                        # not just a prefix of it
+    # a short list is written whole
+    d = str(tmp_path / "c")
+    bench.dump_outputs(d, positions[:1000])
+    assert np.array_equal(np.load(os.path.join(d, "positions.npy")), positions[:1000].astype(np.float64))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_ranks_without_launcher_on_one_gpu(world):
     # gloo: two RCCL ranks cannot share the box's one device
+    # --full: the golden check of the candidates is one of the legs beside the headline
     r = _run(["--gpus", str(world), "--backend", "gloo", "--steps", "2", "--warmup", "1",
-              "--no-cpu", "--no-other"], timeout=600)
+              "--full", "--no-cpu", "--no-other"], timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [s for s in r.stdout.splitlines() if s.startswith("{")]
     assert len(lines) == 1, r.stdout[-4000:]
@@ -108,6 +139,46 @@ def test_bench_ranks_without_launcher_on_one_gpu(world):
     assert line["check"]["match_golden"] is True, line["check"]
     assert line["check"]["ascending"] is True
     assert len(line["multi"]["per_rank_step_ms"]["by_rank"]) == world
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_their_output(tmp_path):
+    # a plain run (no --full) on a 16 MiB buffer: the headline fields, none of
+    # the legs beside it, and --dump-outputs = the oracle's candidates of the
+    # same seeded input
+    import numpy as np
+
+    import oracle
+    from conftest import ref_tables
+    out = str(tmp_path / "dump")
+    n = 1 << 24
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--gib-per-gpu", str(n / 2**30),
+              "--dump-outputs", out], timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [s for s in r.stdout.splitlines() if s.startswith("{")]
+    assert len(lines) == 1, r.stdout[-4000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    ms = line["ms_per_step"]
+    assert ms > 0
+    # value = bytes per step / ms_per_step; the line rounds ms to 1e-4 and value to 1e-3
+    want = n / (ms * 1e-3) / 1e9
+    assert abs(line["value"] - want) <= want * (1e-4 / ms) + 2e-3, (line["value"], want)
+    # one HIP-event time per scan kernel that the timed steps launched and collected
+    assert line["roofline"]["kernel_launches"] == 3
+    # the kernels ran one after another inside the timed window (both figures rounded to 1e-4)
+    assert 0 < line["roofline"]["kernel_ms_avg"] <= ms + 2e-4
+    for leg in ("cpu_baseline", "cpu_baseline_1thread", "cpu_port_parallel", "preverify",
+                "verified_step", "check", "other_rule_sets"):
+        assert line[leg] is None, leg
+    ref = oracle.candidates(ref_tables("C"), oracle.xorshift(n, 1))
+    pos = np.load(os.path.join(out, "positions.npy"))
+    cnt = np.load(os.path.join(out, "count.npy"))
+    assert pos.dtype == np.float64 and cnt.dtype == np.float64
+    assert sorted(os.listdir(out)) == ["count.npy", "positions.npy"]
+    assert ref.size > 0 and cnt.tolist() == [float(ref.size)]
+    assert np.array_equal(pos, ref.astype(np.float64))
 
 
 @pytest.mark.gpu

@@ -1,13 +1,14 @@
 """End-to-end match-set parity against the stock reference libyara.
 
-integration/_build/e2e_check compiles the rules with the stock libyara
+oracle/_ref/e2e_check (integration/Makefile) compiles the rules with the stock libyara
 compiler and scans the same bytes twice: through stock yr_scanner_scan_mem
 (scanner.c:633) and through the re-hosted driver of integration/yr_gpu_scanner.c
 (GPU candidate stream -> reference-ordered replay -> the unmodified
 yr_scan_verify_match / yr_execute_code of that same libyara).  Every match of
 every string ({string, base+offset, length, xor key}) and every rule report
-must be identical.  The reference build (oracle/_ref) and the shim are built
-in the build container and travel to the GPU box as shared objects.
+must be identical.  The reference build, the shim and the checkers need the
+reference tree at build time and all live in oracle/_ref/, which accompanies
+the tree to the GPU machine.
 """
 import json
 import os
@@ -23,12 +24,12 @@ from conftest import ALPHA, GOLDEN, REPO
 
 pytestmark = pytest.mark.gpu
 
-CHECK = os.path.join(REPO, "integration", "_build", "e2e_check")
+CHECK = os.path.join(REPO, "oracle", "_ref", "e2e_check")
 # the same checker built against libyara + integration/libyara-block-scanner.patch:
 # its GPU side calls libyara's OWN yr_scanner_scan_* with the block scanner attached
-CHECK_HOOK = os.path.join(REPO, "integration", "_build", "e2e_check_hook")
+CHECK_HOOK = os.path.join(REPO, "oracle", "_ref", "e2e_check_hook")
 needs_check = pytest.mark.skipif(not os.path.exists(CHECK),
-                                 reason="integration/_build/e2e_check not built "
+                                 reason="oracle/_ref/e2e_check not built "
                                         "(needs the reference headers at build time)")
 
 
@@ -263,7 +264,7 @@ def test_threads_share_one_gpu_rules(tmp_path, rules, block):
 
 
 needs_hook = pytest.mark.skipif(not os.path.exists(CHECK_HOOK),
-                                reason="integration/_build/e2e_check_hook not built "
+                                reason="oracle/_ref/e2e_check_hook not built "
                                        "(oracle/refpatch.mk needs the reference tree)")
 
 
@@ -351,9 +352,9 @@ def test_multi_device_match_set_equals_stock(tmp_path, rules, kind, size, block,
     assert rc == 0
 
 
-CHECK_PROF = os.path.join(REPO, "integration", "_build", "e2e_check_prof")
+CHECK_PROF = os.path.join(REPO, "oracle", "_ref", "e2e_check_prof")
 needs_prof = pytest.mark.skipif(not os.path.exists(CHECK_PROF),
-                                reason="integration/_build/e2e_check_prof not built "
+                                reason="oracle/_ref/e2e_check_prof not built "
                                        "(oracle/refprof.mk needs the reference at build time)")
 
 

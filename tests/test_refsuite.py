@@ -81,7 +81,8 @@ def test_reference_suite_through_gpu(suite, preverify, topdir):
     assert gpu_available()
     p = _run(os.path.join(SUITE, suite + "-gpu"), topdir, {"YR_GPU_PREVERIFY": preverify})
     tail = (p.stdout[-3000:], p.stderr[-3000:])
-    assert p.returncode == 0, tail
+    assert p.returncode == 0, "%s\n%s\noracle/_ref: %s\noracle/_ref/suite: %s" % (
+        tail + (sorted(os.listdir(os.path.dirname(SUITE))), sorted(os.listdir(SUITE))))
     m = re.search(r"refsuite-gpu: (\d+) scans through yr_gpu_scanner, (\d+) GPU rule sets, "
                   r"preverify=(\d)", p.stderr)
     assert m, tail

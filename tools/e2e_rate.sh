@@ -31,7 +31,7 @@ for n in sys.argv[2:]:
 PY
 for r in $SETS; do
   if [ "$BLOCK" = 0 ]; then args=""; else args="$BLOCK 0"; fi
-  E2E_REPEAT=2 timeout -k 10 600 integration/_build/e2e_check $OUT/$r.yar xs:1:$SIZE $args \
+  E2E_REPEAT=2 timeout -k 10 600 oracle/_ref/e2e_check $OUT/$r.yar xs:1:$SIZE $args \
     > $OUT/${r}_b${BLOCK}.json
   echo "$r block=$BLOCK $(cat $OUT/${r}_b${BLOCK}.json)"
 done

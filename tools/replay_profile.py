@@ -51,7 +51,7 @@ def main():
     import oracle
     from conftest import tables_npz
     ref = ctypes.CDLL(os.path.join(REPO, "oracle", "_ref", "libyara_ref.so"), mode=ctypes.RTLD_GLOBAL)
-    shim = ctypes.CDLL(os.path.join(REPO, "integration", "_build", "libyara_gpu_shim.so"))
+    shim = ctypes.CDLL(os.path.join(REPO, "oracle", "_ref", "libyara_gpu_shim.so"))
     ref.yr_initialize()
     n = a.mib << 20
     data = oracle.xorshift(n, 1)
