@@ -435,6 +435,106 @@ int yr_amd_scan_block_verified(
     uint64_t* count);
 
 /*
+ * ---- Batched scans: many independent buffers in one launch ----
+ *
+ * Every call above takes one block and pays its fixed cost -- a scan launch in
+ * which each workgroup first loads the filter, two compaction launches, the
+ * pre-verification launches, two host waits and a D2H copy -- whatever the
+ * block's size.  A batch is n buffers (n >= 0, any sizes including 0) scanned
+ * with ONE scan and ONE pre-verification pass.  The result for buffer k is
+ * exactly what the single-block call returns for that buffer alone: the walk
+ * starts at the root at the buffer's byte 0 (a key straddling two buffers is
+ * no candidate), positions are local (i in (0, size_k], ascending), every
+ * pre-verification test uses the buffer's own bounds and base, a record's
+ * offset is local and its candidate field indexes the buffer's own stream.
+ * Results come back as one array plus CSR offsets [n + 1]: buffer k's entries
+ * are [off[k], off[k + 1]).
+ *
+ * The buffers lie in one device ARENA at 16-byte-aligned starts.  The arena is
+ * scanned as one block; a partition pass then assigns each candidate to its
+ * buffer, drops those in the gaps and decides the first three positions of
+ * every buffer again from the buffer's own bytes.  Results do not depend on
+ * the bytes in the gaps.  At most YR_AMD_BATCH_MAX_BUFFERS buffers; an arena
+ * with arena_size + 1 > YR_AMD_VERIFY_MAX_CANDIDATES (4 GiB and more) returns
+ * YR_AMD_INVALID_ARGUMENT: cut the list into several arenas.
+ * yr_amd_scanner_set_verified_only has no effect on batch scans.
+ */
+#define YR_AMD_BATCH_MAX_BUFFERS 0x7FFFFFFFull
+
+/*
+ * Pure host code: starts[k] for n buffers of sizes[k] bytes -- ascending,
+ * 16-byte aligned, buffer k at [starts[k], starts[k] + sizes[k]) -- and the
+ * arena's size (the end of the last buffer; 0 for n == 0).
+ */
+int yr_amd_batch_layout(
+    const uint64_t* sizes,
+    uint64_t n,
+    uint64_t* starts,
+    uint64_t* arena_size);
+
+/*
+ * Scan a device-resident arena; starts and sizes are HOST arrays (copied).
+ * Asynchronous on the scanner's stream.  Requirements (else
+ * YR_AMD_INVALID_ARGUMENT): d_arena and every start 16-byte aligned, starts
+ * ascending, buffers inside the arena and not overlapping (an empty buffer may
+ * share its start with the next one).
+ */
+int yr_amd_scan_batch_device(
+    yr_amd_scanner* scanner,
+    const uint8_t* d_arena,
+    uint64_t arena_size,
+    const uint64_t* starts,
+    const uint64_t* sizes,
+    uint64_t n);
+
+/*
+ * Result of the last yr_amd_scan_batch_device: synchronises (with the
+ * overflow rerun of yr_amd_scan_device_result underneath), partitions, and
+ * returns a DEVICE pointer to the buffers' local positions, concatenated, and
+ * a HOST pointer to cand_off[n + 1], both owned by the scanner and valid
+ * until its next scan.  Root-accepting rules (every position of every buffer
+ * a candidate): *all_positions = 1 and an empty CSR (all offsets 0).
+ */
+int yr_amd_scan_batch_result(
+    yr_amd_scanner* scanner,
+    const uint64_t** d_positions,
+    const uint64_t** cand_off,
+    int* all_positions);
+
+/*
+ * yr_amd_verify_device for the last completed batch scan: bases[k] =
+ * YR_MEMORY_BLOCK.base of buffer k (HOST array; NULL: all 0).  *d_records is a
+ * DEVICE pointer to the buffers' records concatenated, *rec_off a HOST pointer
+ * to rec_off[n + 1].  Synchronous.  On root-accepting rules it returns
+ * YR_AMD_INVALID_ARGUMENT: callers fall back to per-buffer scans
+ * (integration/yr_gpu_scanner.c).  A batch scan is verified by this call only
+ * and a single-block scan by yr_amd_verify_device only: the other one returns
+ * YR_AMD_INVALID_ARGUMENT.
+ */
+int yr_amd_verify_batch_device(
+    yr_amd_scanner* scanner,
+    const uint64_t* bases,
+    const yr_amd_verify_rec** d_records,
+    const uint64_t** rec_off);
+
+/*
+ * Host convenience: packs the buffers into pinned staging (gaps zeroed), one
+ * H2D copy, batch scan, batch pre-verification, one D2H copy.  *records /
+ * *rec_off are host arrays owned by the scanner (valid until its next call);
+ * buffer k's slice equals yr_amd_scan_block_verified(data[k], sizes[k],
+ * bases[k]).  YR_AMD_INVALID_ARGUMENT on root-accepting rules and when the
+ * packed arena exceeds the limit above.
+ */
+int yr_amd_scan_batch_verified(
+    yr_amd_scanner* scanner,
+    const uint8_t* const* data,
+    const size_t* sizes,
+    const uint64_t* bases,
+    size_t n,
+    const yr_amd_verify_rec** records,
+    const uint64_t** rec_off);
+
+/*
  * ---- Block pipeline ----
  *
  * The block driver of libyara (yr_scanner_scan_mem_blocks, scanner.c:417-583;

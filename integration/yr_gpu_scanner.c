@@ -74,6 +74,14 @@ struct YR_GPU_SCANNER
   uint64_t multi_blocks; /* blocks scanned across the devices (statistics) */
   int trycatch;          /* the scan's !SCAN_FLAGS_NO_TRYCATCH, for _guarded_copy */
   double t_copy, t_gpu, t_replay; /* yr_gpu_scanner_timing */
+  /* yr_gpu_scanner_scan_mem_batch: the records of the buffer about to be
+   * scanned are already present (its arena's batch made them) -- the one
+   * block of the scan replays them instead of scanning */
+  int have_recs;
+  const yr_amd_verify_rec* recs;
+  uint64_t n_recs;
+  uint64_t batch_arena;  /* most bytes per arena */
+  uint64_t batch_arenas; /* arenas scanned (statistics) */
 #ifdef YR_HAVE_BLOCK_SCANNER
   YR_BLOCK_SCANNER block_scanner; /* yr_gpu_scanner_attach */
 #endif
@@ -390,6 +398,7 @@ int yr_gpu_scanner_create(YR_GPU_RULES* g, YR_GPU_SCANNER** out)
   YR_GPU_SCANNER* s = (YR_GPU_SCANNER*) calloc(1, sizeof(YR_GPU_SCANNER));
   if (s == NULL) return ERROR_INSUFFICIENT_MEMORY;
   s->multi_min = YR_GPU_MULTI_MIN_BLOCK;
+  s->batch_arena = YR_GPU_BATCH_ARENA;
   s->trycatch = 1;
   int r = yr_amd_scanner_create(g->tables, NULL, &s->scanner);
   if (r == ERROR_SUCCESS)
@@ -447,6 +456,18 @@ void yr_gpu_scanner_set_multi_min_block(YR_GPU_SCANNER* s, uint64_t bytes)
 uint64_t yr_gpu_scanner_multi_blocks(const YR_GPU_SCANNER* s)
 {
   return s->multi_blocks;
+}
+
+void yr_gpu_scanner_set_batch_arena(YR_GPU_SCANNER* s, uint64_t bytes)
+{
+  /* an arena of `bytes` must pass yr_amd_scan_batch_verified's limit */
+  if (bytes + 1 > YR_AMD_VERIFY_MAX_CANDIDATES) bytes = YR_AMD_VERIFY_MAX_CANDIDATES - 1;
+  s->batch_arena = bytes;
+}
+
+uint64_t yr_gpu_scanner_batch_arenas(const YR_GPU_SCANNER* s)
+{
+  return s->batch_arenas;
 }
 
 static double _now(void)
@@ -677,7 +698,14 @@ static int _direct_block(
   uint64_t n = 0;
   gs->trycatch = !(scanner->flags & SCAN_FLAGS_NO_TRYCATCH);
   double t0 = _now();
-  if (use_multi)
+  if (gs->have_recs)
+  {
+    /* yr_gpu_scanner_scan_mem_batch: this buffer's slice of its arena's
+     * records (the pages were touched before the arena was packed) */
+    recs = gs->recs;
+    n = gs->n_recs;
+  }
+  else if (use_multi)
   {
     /* staged through pinned memory by _guarded_copy (helper threads
      * included): a fault fails the call with ERROR_COULD_NOT_MAP_FILE */
@@ -746,6 +774,7 @@ static int _scan_one_block(
   int fits = split ? _multi_fits(gs, block->size)
                    : (uint64_t) block->size + 1 <= YR_AMD_VERIFY_MAX_CANDIDATES;
   int replay_block = !gs->preverify || !fits;
+  if (gs->have_recs && gs->direct) return _direct_block(scanner, gs, data, block, 0);
   while (replay_block && gs->inflight > 0) FAIL_ON_ERROR(_replay_next(scanner, gs));
   if (replay_block) return _yr_gpu_scan_mem_block(scanner, gs, data, block);
   if (split) gs->multi_blocks++;
@@ -1059,6 +1088,92 @@ int yr_gpu_scanner_scan_mem(
     size_t buffer_size)
 {
   return _scan_mem(scanner, gs, buffer, buffer_size, 1);
+}
+
+/* Can this buffer go into an arena?  (Else: yr_gpu_scanner_scan_mem.) */
+static int _batchable(YR_GPU_SCANNER* gs, size_t size)
+{
+  if ((uint64_t) size > gs->batch_arena) return 0;
+  if (gs->multi != NULL && (uint64_t) size >= gs->multi_min) return 0; /* split across devices */
+  return 1;
+}
+
+int yr_gpu_scanner_scan_mem_batch(
+    YR_SCANNER* scanner,
+    YR_GPU_SCANNER* gs,
+    const uint8_t* const* buffers,
+    const size_t* sizes,
+    size_t n,
+    size_t* n_done)
+{
+  size_t done = 0;
+  int result = ERROR_SUCCESS;
+  if (n_done != NULL) *n_done = 0;
+  if (n > 0 && (buffers == NULL || sizes == NULL)) return ERROR_INVALID_ARGUMENT;
+  /* batches need pre-verification records; root-accepting rules have no
+   * batch pre-verification (yr_amd_verify_batch_device) */
+  yr_amd_tables_info info;
+  FAIL_ON_ERROR(yr_amd_tables_get_info(gs->gpu_rules->tables, &info));
+  const int batches = gs->preverify && !info.root_accepting;
+
+  while (done < n && result == ERROR_SUCCESS)
+  {
+    size_t i = done, j = i;
+    uint64_t bytes = 0;
+    /* the next arena: buffers [i, j) at 16-byte-aligned starts */
+    while (batches && j < n && j - i < YR_AMD_BATCH_MAX_BUFFERS && _batchable(gs, sizes[j]) &&
+           ((bytes + 15) & ~15ull) + sizes[j] <= gs->batch_arena)
+    {
+      /* touch every page inside the trycatch, as _direct_block does before
+       * its H2D: a buffer that faults ends the arena before it and then fails
+       * on its own, with ERROR_COULD_NOT_MAP_FILE (scanner.c:493-496) */
+      int fault = 0;
+      const uint8_t* data = buffers[j];
+      const size_t size = sizes[j];
+      if (data != NULL)
+      {
+        YR_TRYCATCH(
+            !(scanner->flags & SCAN_FLAGS_NO_TRYCATCH),
+            {
+              volatile uint8_t sink = 0;
+              for (size_t o = 0; o < size; o += 4096) sink ^= data[o];
+              if (size > 0) sink ^= data[size - 1];
+              (void) sink;
+            },
+            { fault = 1; });
+      }
+      if (fault || (data == NULL && size > 0)) break;
+      bytes = ((bytes + 15) & ~15ull) + size;
+      j++;
+    }
+    if (j == i)
+    {
+      /* not batchable (or faulting): the per-buffer path */
+      result = yr_gpu_scanner_scan_mem(scanner, gs, buffers[i], sizes[i]);
+      if (result == ERROR_SUCCESS) done++;
+      continue;
+    }
+    const yr_amd_verify_rec* recs = NULL;
+    const uint64_t* off = NULL;
+    double t0 = _now();
+    result = yr_amd_scan_batch_verified(
+        gs->scanner, buffers + i, sizes + i, NULL, j - i, &recs, &off);
+    gs->t_gpu += _now() - t0;
+    if (result != ERROR_SUCCESS) break;
+    gs->batch_arenas++;
+    /* each buffer through the single-block driver, its records present */
+    for (size_t k = i; k < j && result == ERROR_SUCCESS; k++)
+    {
+      gs->have_recs = 1;
+      gs->recs = recs + off[k - i];
+      gs->n_recs = off[k - i + 1] - off[k - i];
+      result = _scan_mem(scanner, gs, buffers[k], sizes[k], 1);
+      gs->have_recs = 0;
+      if (result == ERROR_SUCCESS) done++;
+    }
+  }
+  if (n_done != NULL) *n_done = done;
+  return result;
 }
 
 /* yr_scanner_scan_file (scanner.c:674-688): map, scan, unmap. */

@@ -67,6 +67,32 @@ int yr_gpu_scanner_scan_mem(
     const uint8_t* buffer,
     size_t buffer_size);
 
+/* Many independent buffers (a directory's files, a process's small regions):
+ * observably equal to calling yr_gpu_scanner_scan_mem on each buffer in order
+ * -- the same callbacks in the same order, the same per-buffer match sets and
+ * rule reports, the scanner's timeout applying to each buffer's scan -- but
+ * the GPU work of many buffers is done at once: the list is cut into arenas
+ * (yr_gpu_scanner_set_batch_arena), each scanned and pre-verified by one
+ * yr_amd_scan_batch_verified, and each buffer's records are then replayed by
+ * the single-block driver.  Stops at the first buffer whose scan returns an
+ * error and returns that code; *n_done = the buffers finished before it (n on
+ * success).  With pre-verification off, for root-accepting rules and for a
+ * buffer too large for an arena it takes the per-buffer path. */
+int yr_gpu_scanner_scan_mem_batch(
+    YR_SCANNER* scanner,
+    YR_GPU_SCANNER* gs,
+    const uint8_t* const* buffers,
+    const size_t* sizes,
+    size_t n,
+    size_t* n_done);
+
+/* The most bytes one arena of yr_gpu_scanner_scan_mem_batch holds (default
+ * YR_GPU_BATCH_ARENA, 1 GiB; always below the limit of yr_amd_scan_batch_*). */
+#define YR_GPU_BATCH_ARENA (1ull << 30)
+void yr_gpu_scanner_set_batch_arena(YR_GPU_SCANNER* s, uint64_t bytes);
+/* How many arenas this scanner has scanned (statistics). */
+uint64_t yr_gpu_scanner_batch_arenas(const YR_GPU_SCANNER* s);
+
 #ifdef YR_HAVE_BLOCK_SCANNER
 /* libyara patched with integration/libyara-block-scanner.patch: make the
  * scanner's own driver (yr_scanner_scan_mem / _mem_blocks / _file / _fd /

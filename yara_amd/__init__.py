@@ -24,7 +24,7 @@ from ._lib import (CALLBACK_ERROR, COULD_NOT_MAP_FILE, INSUFFICIENT_MEMORY,  # n
                    YaraAmdError)
 
 __all__ = ["Tables", "Scanner", "Pipeline", "replay", "fill_xorshift64", "version",
-           "YaraAmdError"]
+           "batch_layout", "YaraAmdError"]
 
 
 def _arr(a, dt):
@@ -33,6 +33,19 @@ def _arr(a, dt):
 
 def version() -> str:
     return _lib.lib().yr_amd_version().decode()
+
+
+def batch_layout(sizes):
+    """(starts uint64[n], arena_size) of a batch of buffers of ``sizes`` bytes
+    (yr_amd_batch_layout): ascending 16-byte-aligned starts, buffer k at
+    [starts[k], starts[k] + sizes[k])."""
+    sz = _arr(sizes, np.uint64).reshape(-1)
+    st = np.zeros(sz.size, np.uint64)
+    arena = ctypes.c_uint64()
+    _lib.check("yr_amd_batch_layout", _lib.lib().yr_amd_batch_layout(
+        sz.ctypes.data_as(_lib._u64p) if sz.size else None, sz.size,
+        st.ctypes.data_as(_lib._u64p) if sz.size else None, ctypes.byref(arena)))
+    return st, arena.value
 
 
 class Tables:
@@ -197,6 +210,7 @@ class Scanner:
                                                     ctypes.byref(h)))
         self._h = h
         self.tables = tables
+        self._batch_n = 0   # buffers of the last scan_batch_device
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -260,6 +274,91 @@ class Scanner:
                    _lib.lib().yr_amd_verify_device(self._h, data_base, ctypes.byref(p),
                                                    ctypes.byref(cnt)))
         return p.value or 0, cnt.value
+
+    # -- batches: N independent buffers, one scan, one pre-verification -------
+    def scan_batch_device(self, d_ptr: int, arena_size: int, starts, sizes):
+        """Scan a device-resident arena holding buffer k at [starts[k], +sizes[k])
+        (yr_amd_scan_batch_device; asynchronous)."""
+        st = _arr(starts, np.uint64).reshape(-1)
+        sz = _arr(sizes, np.uint64).reshape(-1)
+        if st.size != sz.size:
+            raise ValueError("starts and sizes differ in length")
+        _lib.check("yr_amd_scan_batch_device", _lib.lib().yr_amd_scan_batch_device(
+            self._h, ctypes.c_void_p(d_ptr or None), arena_size,
+            st.ctypes.data_as(_lib._u64p) if st.size else None,
+            sz.ctypes.data_as(_lib._u64p) if sz.size else None, st.size))
+        self._batch_n = st.size
+
+    def batch_result(self):
+        """(local positions uint64[], offsets uint64[n + 1], all_positions) of the
+        last scan_batch_device (yr_amd_scan_batch_result), copied to the host."""
+        from ._hip import d2h_u64
+        p = ctypes.c_void_p()
+        off = ctypes.POINTER(ctypes.c_uint64)()
+        allp = ctypes.c_int()
+        _lib.check("yr_amd_scan_batch_result", _lib.lib().yr_amd_scan_batch_result(
+            self._h, ctypes.byref(p), ctypes.byref(off), ctypes.byref(allp)))
+        offsets = np.ctypeslib.as_array(off, shape=(self._batch_n + 1,)).copy()
+        return d2h_u64(p.value or 0, int(offsets[-1])), offsets, bool(allp.value)
+
+    def verify_batch_device(self, bases=None):
+        """(records {offset, pool_index, candidate}, offsets uint64[n + 1]) of the
+        last completed batch scan (yr_amd_verify_batch_device), copied to the host."""
+        from ._hip import memcpy
+        b = None if bases is None else _arr(bases, np.uint64).reshape(-1)
+        if b is not None and b.size != self._batch_n:
+            raise ValueError("one base per buffer")
+        p = ctypes.c_void_p()
+        off = ctypes.POINTER(ctypes.c_uint64)()
+        _lib.check("yr_amd_verify_batch_device", _lib.lib().yr_amd_verify_batch_device(
+            self._h, b.ctypes.data_as(_lib._u64p) if b is not None and b.size else None,
+            ctypes.byref(p), ctypes.byref(off)))
+        offsets = np.ctypeslib.as_array(off, shape=(self._batch_n + 1,)).copy()
+        out = np.zeros(int(offsets[-1]), dtype=_lib.VERIFY_REC_DTYPE)
+        memcpy(out.ctypes.data, p.value or 0, out.size * 16, 2)
+        return out, offsets
+
+    def batch_candidates(self, buffers):
+        """(positions, offsets, all_positions) of a list of host buffers: buffer
+        k's candidate positions -- local, exactly ``candidates(buffers[k])[0]``
+        -- are positions[offsets[k]:offsets[k + 1]].  One scan for all of them."""
+        from . import _hip
+        bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
+        sizes = np.array([b.size for b in bufs], np.uint64)
+        starts, arena = batch_layout(sizes)
+        host = np.zeros(max(arena, 1), np.uint8)   # (gaps zeroed)
+        for b, s in zip(bufs, starts):
+            host[int(s):int(s) + b.size] = b
+        d = _hip.malloc(arena)
+        try:
+            _hip.memcpy(d, host.ctypes.data, arena, 1)
+            self.scan_batch_device(d, arena, starts, sizes)
+            return self.batch_result()
+        finally:
+            _hip.hip().hipDeviceSynchronize()
+            _hip.free(d)
+
+    def batch_verify_calls(self, buffers, bases=None):
+        """(records, offsets) of a list of host buffers
+        (yr_amd_scan_batch_verified): records[offsets[k]:offsets[k + 1]] equals
+        ``verify_calls(buffers[k], bases[k])``."""
+        bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
+        n = len(bufs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        sizes = (ctypes.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        b = None if bases is None else _arr(bases, np.uint64).reshape(-1)
+        if b is not None and b.size != n:
+            raise ValueError("one base per buffer")
+        rec = ctypes.POINTER(_lib.VerifyRec)()
+        off = ctypes.POINTER(ctypes.c_uint64)()
+        _lib.check("yr_amd_scan_batch_verified", _lib.lib().yr_amd_scan_batch_verified(
+            self._h, ptrs, sizes, b.ctypes.data_as(_lib._u64p) if b is not None and b.size else None,
+            n, ctypes.byref(rec), ctypes.byref(off)))
+        offsets = np.ctypeslib.as_array(off, shape=(n + 1,)).copy()
+        out = np.zeros(int(offsets[-1]), dtype=_lib.VERIFY_REC_DTYPE)
+        if out.size:
+            ctypes.memmove(out.ctypes.data, rec, out.size * 16)
+        return out, offsets
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

@@ -26,6 +26,10 @@ def hip():
         _hip.hipMemcpy.restype = ctypes.c_int
         _hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
         _hip.hipDeviceSynchronize.restype = ctypes.c_int
+        _hip.hipMalloc.restype = ctypes.c_int
+        _hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        _hip.hipFree.restype = ctypes.c_int
+        _hip.hipFree.argtypes = [ctypes.c_void_p]
     return _hip
 
 
@@ -35,6 +39,19 @@ def memcpy(dst: int, src: int, nbytes: int, kind: int):
         rc = hip().hipMemcpy(ctypes.c_void_p(dst), ctypes.c_void_p(src), nbytes, kind)
         if rc != 0:
             raise RuntimeError("hipMemcpy failed: %d" % rc)
+
+
+def malloc(nbytes: int) -> int:
+    p = ctypes.c_void_p()
+    rc = hip().hipMalloc(ctypes.byref(p), max(nbytes, 16))
+    if rc != 0:
+        raise MemoryError("hipMalloc(%d) failed: %d" % (nbytes, rc))
+    return p.value
+
+
+def free(ptr: int):
+    if ptr:
+        hip().hipFree(ctypes.c_void_p(ptr))
 
 
 def d2h_u64(ptr: int, count: int) -> np.ndarray:

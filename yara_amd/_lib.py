@@ -124,6 +124,15 @@ PROTOTYPES = {
     "yr_amd_multi_scan_block_verified": (_int, [_vp, _u8p, ctypes.c_size_t, ctypes.c_uint64,
                                                 ctypes.POINTER(ctypes.POINTER(VerifyRec)),
                                                 ctypes.POINTER(ctypes.c_uint64)]),
+    "yr_amd_batch_layout": (_int, [_u64p, ctypes.c_uint64, _u64p, _u64p]),
+    "yr_amd_scan_batch_device": (_int, [_vp, _vp, ctypes.c_uint64, _u64p, _u64p, ctypes.c_uint64]),
+    "yr_amd_scan_batch_result": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u64p),
+                                        ctypes.POINTER(_int)]),
+    "yr_amd_verify_batch_device": (_int, [_vp, _u64p, ctypes.POINTER(_vp), ctypes.POINTER(_u64p)]),
+    "yr_amd_scan_batch_verified": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t),
+                                          _u64p, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.POINTER(VerifyRec)),
+                                          ctypes.POINTER(_u64p)]),
     "yr_amd_tables_device": (_int, [_vp]),
     "yr_amd_tables_set_profiling": (_int, [_vp, _int]),
 }

@@ -22,6 +22,7 @@
 #include "tables.h"
 #include "re_program.h"
 #include "verify.h"
+#include "batch.h"
 
 namespace yamd {
 hipError_t launch_scan(const ScanParams& p, int grid, hipStream_t s, int mode, hipEvent_t t0 = nullptr,
@@ -204,6 +205,27 @@ struct yr_amd_scanner {
   VerifyRec* d_vrec = nullptr;
   size_t vrec_cap = 0;
   std::vector<yr_amd_verify_rec> h_vrec;
+
+  // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
+  // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
+  bool batch = false, batch_done = false;
+  uint32_t batch_n = 0;
+  uint64_t batch_count = 0;             // kept candidates of the batch
+  uint64_t* d_bstarts = nullptr;        // [3 * n]: starts, sizes, bases
+  size_t bstarts_cap = 0;
+  uint64_t* d_boff = nullptr;           // [2 * (n + 1)]: cand_off, rec_off
+  size_t boff_cap = 0;
+  uint32_t* d_btmp = nullptr;           // [3 * count]: BatchParams tmp_buf, out_buf, out_index
+  size_t btmp_cap = 0;
+  uint64_t* d_bpos = nullptr;           // [count] local positions
+  size_t bpos_cap = 0;
+  uint32_t* d_bunit = nullptr;          // [units] BatchParams::unit_count
+  size_t bunit_cap = 0;
+  uint64_t* d_bunit_off = nullptr;      // [units + 1]
+  size_t bunit_off_cap = 0;
+  std::vector<uint64_t> h_bstarts, h_bsizes, h_bases, h_cand_off, h_rec_off;
+  uint8_t* h_arena = nullptr;           // pinned staging of yr_amd_scan_batch_verified
+  size_t h_arena_cap = 0;
 };
 
 static_assert(sizeof(VerifyRec) == sizeof(yr_amd_verify_rec), "record layout");
@@ -463,8 +485,11 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_summary,
                   (void*)s->d_vcount, (void*)s->d_vkeep, (void*)s->d_vblock, (void*)s->d_vrec,
                   (void*)s->d_vchunk, (void*)s->d_seg_base,
-                  (void*)s->d_seg_next, (void*)s->d_trace_T, (void*)s->d_trace_M})
+                  (void*)s->d_seg_next, (void*)s->d_trace_T, (void*)s->d_trace_M,
+                  (void*)s->d_bstarts, (void*)s->d_boff, (void*)s->d_btmp, (void*)s->d_bpos,
+                  (void*)s->d_bunit, (void*)s->d_bunit_off})
     if (p) (void)hipFree(p);
+  if (s->h_arena) (void)hipHostFree(s->h_arena);
   if (s->h_summary) (void)hipHostFree(s->h_summary);
   if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
   if (s->ev_end) (void)hipEventDestroy(s->ev_end);
@@ -582,6 +607,8 @@ int yr_amd_scan_window(yr_amd_scanner* s, const uint8_t* d_window, uint64_t wind
     return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_tables* t = s->tables;
   s->pending = true;
+  s->batch = false;
+  s->batch_done = false;
   s->last_count = 0;
   s->last_full_count = 0;
   s->ev_valid = false;
@@ -1423,6 +1450,8 @@ int yr_amd_tables_set_re_code(yr_amd_tables* t, uint32_t n_pool, const uint32_t*
 int yr_amd_verify_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_verify_rec** d_records,
                          uint64_t* count) {
   if (s == nullptr || s->pending || !s->tables->has_strings) return YR_AMD_INVALID_ARGUMENT;
+  // (a batch's candidates belong to its buffers: yr_amd_verify_batch_device)
+  if (s->batch) return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_tables* t = s->tables;
   const ScanParams& L = s->last;
   HIP_TRY(hipSetDevice(t->device));
@@ -1583,6 +1612,253 @@ int yr_amd_scan_block_verified(yr_amd_scanner* s, const uint8_t* data, size_t si
   }
   if (records) *records = s->h_vrec.data();
   if (count) *count = n;
+  return YR_AMD_SUCCESS;
+}
+
+// ---- Batched scans: N buffers in one arena, one scan, one pre-verification ----
+
+int yr_amd_batch_layout(const uint64_t* sizes, uint64_t n, uint64_t* starts, uint64_t* arena_size) {
+  if (n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (sizes == nullptr || starts == nullptr)))
+    return YR_AMD_INVALID_ARGUMENT;
+  uint64_t at = 0, end = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (sizes[k] > UINT64_MAX - 15 - at) return YR_AMD_INVALID_ARGUMENT;
+    starts[k] = at;
+    end = at + sizes[k];
+    at = (end + 15) & ~15ull;
+  }
+  if (arena_size) *arena_size = end;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_batch_device(yr_amd_scanner* s, const uint8_t* d_arena, uint64_t arena_size,
+                             const uint64_t* starts, const uint64_t* sizes, uint64_t n) {
+  if (s == nullptr || n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (starts == nullptr || sizes == nullptr)))
+    return YR_AMD_INVALID_ARGUMENT;
+  // (an arena of arena_size bytes has at most arena_size + 1 candidates, and
+  // records index candidates in 32 bits)
+  if (arena_size >= YR_AMD_VERIFY_MAX_CANDIDATES) return YR_AMD_INVALID_ARGUMENT;
+  if ((((uintptr_t)d_arena) & 15) != 0 || (d_arena == nullptr && arena_size > 0))
+    return YR_AMD_INVALID_ARGUMENT;
+  uint64_t prev_end = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    if ((starts[k] & 15) != 0 || starts[k] < prev_end || sizes[k] > arena_size ||
+        starts[k] > arena_size - sizes[k])
+      return YR_AMD_INVALID_ARGUMENT;
+    prev_end = starts[k] + sizes[k];
+  }
+  HIP_TRY(hipSetDevice(s->tables->device));
+  s->h_bstarts.assign(starts, starts + n);
+  s->h_bsizes.assign(sizes, sizes + n);
+  int r = grow(s->d_bstarts, s->bstarts_cap, 3 * (size_t)n);
+  if (r) return r;
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(s->d_bstarts, s->h_bstarts.data(), n * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_bstarts + n, s->h_bsizes.data(), n * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, s->stream));
+  }
+  // the arena as one block, its full stream: a verified-only scan leaves
+  // candidates out by classes decided from bytes that, in an arena, may lie in
+  // a gap or in the next buffer
+  const bool was = s->verified_only;
+  s->verified_only = false;
+  r = yr_amd_scan_device(s, d_arena, arena_size, 0, arena_size);
+  s->verified_only = was;
+  if (r) return r;
+  s->batch = true;
+  s->batch_done = false;
+  s->batch_n = (uint32_t)n;
+  s->batch_count = 0;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_batch_result(yr_amd_scanner* s, const uint64_t** d_positions,
+                             const uint64_t** cand_off, int* all_positions) {
+  if (s == nullptr || !s->batch || !s->pending) return YR_AMD_INVALID_ARGUMENT;
+  const uint64_t* d_pos = nullptr;
+  uint64_t count = 0;
+  int all = 0;
+  int r = yr_amd_scan_device_result(s, &d_pos, &count, &all);   // (the overflow rerun included)
+  if (r) return r;
+  const uint32_t n = s->batch_n;
+  s->h_cand_off.assign((size_t)n + 1, 0);
+  s->batch_count = 0;
+  if (!all && count > 0 && n > 0) {
+    const yr_amd_tables* t = s->tables;
+    const uint64_t units = (count + kBatchUnit - 1) / kBatchUnit;
+    r = grow(s->d_btmp, s->btmp_cap, 3 * count);
+    if (!r) r = grow(s->d_bpos, s->bpos_cap, count);
+    if (!r) r = grow(s->d_bunit, s->bunit_cap, units);
+    if (!r) r = grow(s->d_bunit_off, s->bunit_off_cap, units + 1);
+    if (!r) r = grow(s->d_boff, s->boff_cap, 2 * ((size_t)n + 1));
+    if (r) return r;
+    BatchParams b{};
+    b.positions = d_pos;
+    b.count = count;
+    b.units = units;
+    b.data = s->last.data;
+    b.starts = s->d_bstarts;
+    b.sizes = s->d_bstarts + n;
+    b.n = n;
+    b.exact = t->d_exact;
+    b.t3_off = t->flat.t3_off;
+    b.t3_mask = t->flat.t3_mask;
+    b.len_mask = t->flat.len_mask;
+    b.tmp_buf = s->d_btmp;
+    b.out_buf = s->d_btmp + count;
+    b.out_index = s->d_btmp + 2 * count;
+    b.unit_count = s->d_bunit;
+    b.unit_off = s->d_bunit_off;
+    b.out_pos = s->d_bpos;
+    b.cand_off = s->d_boff;
+    HIP_TRY(launch_batch_partition(b, s->d_summary, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_cand_off.data(), s->d_boff, ((size_t)n + 1) * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->batch_count = s->h_cand_off[n];
+  }
+  s->batch_done = true;
+  if (d_positions) *d_positions = s->d_bpos;
+  if (cand_off) *cand_off = s->h_cand_off.data();
+  if (all_positions) *all_positions = all;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_verify_batch_device(yr_amd_scanner* s, const uint64_t* bases,
+                               const yr_amd_verify_rec** d_records, const uint64_t** rec_off) {
+  if (s == nullptr || s->pending || !s->batch || !s->batch_done || !s->tables->has_strings)
+    return YR_AMD_INVALID_ARGUMENT;
+  // root-accepting rules: every position of every buffer is a candidate and
+  // the batch holds no stream -- scan such buffers one by one
+  if (s->last_all) return YR_AMD_INVALID_ARGUMENT;
+  const yr_amd_tables* t = s->tables;
+  HIP_TRY(hipSetDevice(t->device));
+  const uint32_t n = s->batch_n;
+  const uint64_t count = s->batch_count, arena_count = s->last_count;
+  s->h_rec_off.assign((size_t)n + 1, 0);
+  uint64_t total = 0;
+  if (count > 0) {
+    if (bases != nullptr) {
+      s->h_bases.assign(bases, bases + n);
+      HIP_TRY(hipMemcpyAsync(s->d_bstarts + 2 * (size_t)n, s->h_bases.data(), n * sizeof(uint64_t),
+                             hipMemcpyHostToDevice, s->stream));
+    }
+    BatchView view{s->d_bstarts, s->d_bstarts + n, bases != nullptr ? s->d_bstarts + 2 * (size_t)n : nullptr,
+                   s->d_btmp + arena_count};
+    VerifyParams v{};
+    v.data = s->last.data;
+    v.size = s->last.block_size;   // (each candidate sees its buffer: verify.hip batch_view)
+    v.win_lo = 0;
+    v.win_hi = v.size;
+    v.positions = s->d_bpos;
+    v.count = count;
+    v.cand_index = s->d_btmp + 2 * arena_count;
+    const FlatTables& f = t->flat;
+    v.nodes = t->d_nodes;
+    v.n3_off = f.n3_off;
+    v.n3_mask = f.n3_mask;
+    v.n4_off = f.n4_off;
+    v.n4_mask = f.n4_mask;
+    v.root_head = f.M[0];
+    v.pool = t->d_pool;
+    v.str_bytes = t->d_str_bytes;
+    v.lowercase = t->d_lowercase;
+    v.re_on = t->d_re_code != nullptr ? 1 : 0;
+    v.profile = t->profile ? 1 : 0;
+    v.re_code = t->d_re_code;
+    int r = grow(s->d_vcount, s->vcount_cap, count);
+    if (!r) r = grow(s->d_vkeep, s->vkeep_cap, 2 * count);
+    if (!r) r = grow(s->d_vblock, s->vblock_cap, verify_groups(count) + 1);
+    if (!r) r = grow(s->d_vchunk, s->vchunk_cap, verify_chunks(count) + 1);
+    if (!r) r = grow(s->d_vrec, s->vrec_cap, std::min<uint64_t>(count / 16 + 1, 1u << 20));
+    if (r) return r;
+    v.counts = s->d_vcount;
+    v.keep = s->d_vkeep;
+    v.heads = s->d_vkeep + count;
+    v.block_off = s->d_vblock;
+    v.chunk_off = s->d_vchunk;
+    v.out = s->d_vrec;
+    v.out_cap = s->vrec_cap;
+    // count pass -> offsets -> write pass and the buffers' record offsets, one wait
+    HIP_TRY(launch_verify_batch(v, view, 0, s->stream));
+    HIP_TRY(launch_block_offsets(s->d_vblock, s->d_vchunk, count, s->d_hsum, nullptr,
+                                 KeptLists{{0, 0, 0, 0}}, s->stream));
+    HIP_TRY(launch_verify_batch(v, view, 1, s->stream));
+    uint64_t* d_rec_off = s->d_boff + (size_t)n + 1;
+    HIP_TRY(launch_batch_rec_offsets(v, s->d_boff, n, d_rec_off, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_rec_off.data(), d_rec_off, ((size_t)n + 1) * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    total = s->h_summary[0];
+    if (total != s->h_rec_off[n]) return YR_AMD_INTERNAL_FATAL_ERROR;
+    if (total > v.out_cap) {
+      r = grow(s->d_vrec, s->vrec_cap, std::max<uint64_t>(total, 2 * s->vrec_cap));
+      if (r) return r;
+      v.out = s->d_vrec;
+      v.out_cap = s->vrec_cap;
+      HIP_TRY(launch_verify_batch(v, view, 1, s->stream));
+      HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+  }
+  if (debug_level() >= 1)
+    fprintf(stderr, "- %u buffers, %llu candidates -> %llu verify calls // yr_amd_verify_batch_device()\n",
+            n, (unsigned long long)count, (unsigned long long)total);
+  if (d_records) *d_records = reinterpret_cast<const yr_amd_verify_rec*>(s->d_vrec);
+  if (rec_off) *rec_off = s->h_rec_off.data();
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_batch_verified(yr_amd_scanner* s, const uint8_t* const* data, const size_t* sizes,
+                               const uint64_t* bases, size_t n, const yr_amd_verify_rec** records,
+                               const uint64_t** rec_off) {
+  if (s == nullptr || n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (data == nullptr || sizes == nullptr)))
+    return YR_AMD_INVALID_ARGUMENT;
+  if (!s->tables->has_strings || s->tables->flat.root_accepting) return YR_AMD_INVALID_ARGUMENT;
+  std::vector<uint64_t> sz(n), st(n);
+  for (size_t k = 0; k < n; ++k) {
+    if (data[k] == nullptr && sizes[k] > 0) return YR_AMD_INVALID_ARGUMENT;
+    sz[k] = sizes[k];
+  }
+  uint64_t arena = 0;
+  int r = yr_amd_batch_layout(sz.data(), n, st.data(), &arena);
+  if (r) return r;
+  if (arena >= YR_AMD_VERIFY_MAX_CANDIDATES) return YR_AMD_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(s->tables->device));
+  if (arena > s->h_arena_cap) {
+    if (s->h_arena) (void)hipHostFree(s->h_arena);
+    s->h_arena = nullptr;
+    s->h_arena_cap = 0;
+    if (hipHostMalloc((void**)&s->h_arena, arena, hipHostMallocDefault) != hipSuccess)
+      return YR_AMD_INSUFFICIENT_MEMORY;
+    s->h_arena_cap = arena;
+  }
+  // the buffers at their starts, the gaps between them zeroed
+  for (size_t k = 0; k < n; ++k) {
+    if (sz[k] > 0) memcpy(s->h_arena + st[k], data[k], sz[k]);
+    const uint64_t end = st[k] + sz[k], next = k + 1 < n ? st[k + 1] : arena;
+    if (next > end) memset(s->h_arena + end, 0, next - end);
+  }
+  r = grow(s->d_block, s->d_block_cap, std::max<size_t>(arena, 16));
+  if (r) return r;
+  if (arena > 0 &&
+      hipMemcpyAsync(s->d_block, s->h_arena, arena, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+    return YR_AMD_COULD_NOT_MAP_FILE;
+  r = yr_amd_scan_batch_device(s, s->d_block, arena, st.data(), sz.data(), n);
+  if (!r) r = yr_amd_scan_batch_result(s, nullptr, nullptr, nullptr);
+  const yr_amd_verify_rec* d_rec = nullptr;
+  const uint64_t* off = nullptr;
+  if (!r) r = yr_amd_verify_batch_device(s, bases, &d_rec, &off);
+  if (r) return r;
+  const uint64_t total = off[n];
+  s->h_vrec.resize(total);
+  if (total > 0) {
+    HIP_TRY(hipMemcpyAsync(s->h_vrec.data(), d_rec, total * sizeof(yr_amd_verify_rec),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  if (records) *records = s->h_vrec.data();
+  if (rec_off) *rec_off = off;
   return YR_AMD_SUCCESS;
 }
 

@@ -26,6 +26,7 @@
 #include <mutex>
 #include <vector>
 
+#include "batch.h"
 #include "internal.h"
 #include "re_program.h"
 #include "verify.h"
@@ -1255,6 +1256,112 @@ __global__ __launch_bounds__(1024) void block_offsets_kernel(uint64_t* block_off
     block_off[n_blocks] = part[1023];
     *total = part[1023];
   }
+}
+
+// ---------------------------------------------------------------------------
+// Batch pre-verification (yr_amd_verify_batch_device): the candidates of N
+// buffers in one stream (batch.hip), positions local to each buffer.  Every
+// candidate is decided against a view of the parameters that holds its own
+// buffer as the whole block -- data, size, window and base -- so each test of
+// call_matters (offset == size, FULL_WORD at the block's ends, the regexp scan
+// limits, FIXED_OFFSET) sees the buffer's bounds and never a byte outside it.
+// Buffers start 16-byte aligned, as node_head and stage_window assume of a
+// block.  No candidate classes (VerifyParams::dead / live null): the scan
+// decides those from bytes next to the key, which in an arena may be another
+// buffer's.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ VerifyParams batch_view(const VerifyParams& p, const BatchView& b,
+                                                   uint64_t c) {
+  VerifyParams q = p;
+  const uint32_t k = b.cand_buf[c];
+  q.data = p.data + b.starts[k];
+  q.size = b.sizes[k];
+  q.win_lo = 0;
+  q.win_hi = q.size;
+  q.data_base = b.bases != nullptr ? b.bases[k] : 0ull;
+  return q;
+}
+
+// PASS 0: one candidate per lane (verify_kernel<0>).  PASS 1: one wave per
+// group of 64 candidates (p.first: the launch's first group); a group without
+// records reads its two offsets only.
+template <int PASS>
+__global__ __launch_bounds__(256) void verify_batch_kernel(VerifyParams p, BatchView b) {
+  __shared__ __attribute__((aligned(16))) uint8_t win[256 * kWinBytes];
+  __shared__ __attribute__((aligned(16))) uint8_t code[256 * kCodeBytes];
+  const uint32_t lds = (uint32_t)(uintptr_t)(win + threadIdx.x * kWinBytes);
+  const uint32_t codebuf = (uint32_t)(uintptr_t)(code + threadIdx.x * kCodeBytes);
+  const uint64_t groups = (p.count + kGroup - 1) / kGroup;
+  if (PASS == 0) {
+    const uint64_t c = p.first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t n = 0;
+    if (c < p.count) {
+      const VerifyParams q = batch_view(p, b, c);
+      verify_one<0>(q, c, lds, codebuf, 0, 0, 0, n);
+    }
+    const uint32_t sum = wave_sum(n);
+    if ((threadIdx.x & 63u) == 0 && c / kGroup < groups) p.block_off[c / kGroup] = sum;
+    return;
+  }
+  const uint64_t g = p.first + (uint64_t)blockIdx.x * (blockDim.x / 64) + wave_in_block();
+  if (g >= groups) return;
+  const uint64_t o = group_offset(p, g);
+  if (group_offset(p, g + 1) == o) return;   // (wave-uniform)
+  const uint64_t c = g * kGroup + (threadIdx.x & 63u);
+  uint32_t keep = 0, n = 0, head = 0;
+  if (c < p.count) {
+    keep = p.keep[c];
+    if (keep != 0) {
+      n = p.counts[c];
+      head = p.heads[c];
+    }
+  }
+  const uint32_t pre = wave_exclusive(n);
+  if (keep != 0) {
+    const VerifyParams q = batch_view(p, b, c);
+    verify_one<1>(q, c, lds, codebuf, keep, head, o + pre, n);
+  }
+}
+
+// rec_off[k], k in [0, n]: the records before buffer k's first candidate --
+// its group's offset plus the counts of the group's candidates before it.
+__global__ __launch_bounds__(256) void batch_rec_offsets_kernel(VerifyParams p,
+                                                                const uint64_t* cand_off, uint32_t n,
+                                                                uint64_t* rec_off) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > n) return;
+  const uint64_t c0 = cand_off[k], g = c0 / kGroup;
+  uint64_t o = group_offset(p, g);   // (g == groups: the entry past the last group, the total)
+  for (uint64_t c = g * kGroup; c < c0; ++c)
+    if (p.keep[c] != 0) o += p.counts[c];
+  rec_off[k] = o;
+}
+
+hipError_t launch_verify_batch(const VerifyParams& p, const BatchView& b, int pass, hipStream_t s) {
+  if (p.count == 0) return hipSuccess;
+  VerifyParams q = p;
+  if (pass == 0) {
+    constexpr uint64_t kSlice = 1ull << 31;   // (launch_verify: 32-bit grids, whole groups)
+    for (q.first = 0; q.first < p.count; q.first += kSlice) {
+      const uint64_t n = std::min<uint64_t>(p.count - q.first, kSlice);
+      hipLaunchKernelGGL(verify_batch_kernel<0>, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, q, b);
+    }
+  } else {
+    constexpr uint64_t kSliceGroups = (1ull << 31) / kGroup;
+    const uint64_t groups = verify_groups(p.count);
+    for (q.first = 0; q.first < groups; q.first += kSliceGroups) {
+      const uint64_t n = std::min<uint64_t>(groups - q.first, kSliceGroups);
+      hipLaunchKernelGGL(verify_batch_kernel<1>, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, s, q, b);
+    }
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_rec_offsets(const VerifyParams& p, const uint64_t* cand_off, uint32_t n,
+                                    uint64_t* rec_off, hipStream_t s) {
+  hipLaunchKernelGGL(batch_rec_offsets_kernel, dim3((uint32_t)(((uint64_t)n + 1 + 255) / 256)),
+                     dim3(256), 0, s, p, cand_off, n, rec_off);
+  return hipGetLastError();
 }
 
 // Grid of the persistent kernels: as many 256-thread blocks as the device
