@@ -535,6 +535,55 @@ int yr_amd_scan_batch_verified(
     const uint64_t** rec_off);
 
 /*
+ * ---- Batches of buffers scattered in device memory ----
+ *
+ * The arena calls above take ONE allocation.  Buffers that already sit in
+ * device memory as separate pieces at any addresses -- archive members
+ * unpacked on the GPU, tensors, slices of a capture buffer at odd byte
+ * offsets -- are packed into an arena by one kernel launch, whatever n:
+ *
+ * yr_amd_batch_gather copies buffer k, the sizes[k] bytes at d_buffers[k], to
+ * [starts[k], starts[k] + sizes[k]) of d_arena and writes every other byte of
+ * [0, arena_size) as zero (the gaps: what the host convenience does with its
+ * staging), so the packed arena is a function of the buffers alone.  No byte
+ * at or beyond arena_size is written and no byte outside a buffer is read.
+ * starts, sizes and d_buffers are HOST arrays (copied); d_buffers holds DEVICE
+ * addresses of any alignment, dereferenceable from the tables' device.
+ * Requirements (else YR_AMD_INVALID_ARGUMENT, checked before any work): those
+ * of yr_amd_scan_batch_device on d_arena, arena_size, starts, sizes and n, and
+ * no null buffer of a non-zero size.  Asynchronous on the scanner's stream.
+ * The call touches no scan state: it may run between a scan and its results.
+ */
+int yr_amd_batch_gather(
+    yr_amd_scanner* scanner,
+    uint8_t* d_arena,
+    uint64_t arena_size,
+    const uint64_t* starts,
+    const uint8_t* const* d_buffers,
+    const uint64_t* sizes,
+    uint64_t n);
+
+/*
+ * yr_amd_batch_layout, yr_amd_batch_gather into an arena the scanner owns and
+ * yr_amd_scan_batch_device on it, in one asynchronous call.  Results through
+ * yr_amd_scan_batch_result and yr_amd_verify_batch_device, exactly those of
+ * the arena calls (and of yr_amd_scan_batch_verified on host copies of the
+ * buffers).  YR_AMD_INVALID_ARGUMENT when the packed arena exceeds the limit
+ * above.
+ *   Lifetime: the buffers must stay valid and unchanged until
+ * yr_amd_scan_batch_result has returned; after that the scanner reads only
+ * its arena (yr_amd_verify_batch_device included).
+ *   Ordering: the work runs on the scanner's stream.  Whatever produces the
+ * buffers must be ordered before it by the caller: create the scanner on the
+ * producer's stream, or synchronise the producer first.
+ */
+int yr_amd_scan_batch_gather_device(
+    yr_amd_scanner* scanner,
+    const uint8_t* const* d_buffers,
+    const uint64_t* sizes,
+    uint64_t n);
+
+/*
  * ---- Block pipeline ----
  *
  * The block driver of libyara (yr_scanner_scan_mem_blocks, scanner.c:417-583;

@@ -48,6 +48,25 @@ def batch_layout(sizes):
     return st, arena.value
 
 
+def _device_buffers(buffers):
+    """(ptrs uint64[n], sizes uint64[n]) of a list of device buffers: (ptr, size)
+    pairs and tensor-like objects of 1-byte elements."""
+    ptrs, sizes = [], []
+    for b in buffers:
+        if isinstance(b, (tuple, list)):
+            ptr, size = b
+        else:
+            if b.element_size() != 1:
+                raise ValueError("a device buffer holds bytes: element size %d" % b.element_size())
+            if not b.is_contiguous():
+                raise ValueError("a device buffer is contiguous")
+            size = b.numel()
+            ptr = b.data_ptr() if size else 0
+        ptrs.append(int(ptr))
+        sizes.append(int(size))
+    return np.array(ptrs, np.uint64), np.array(sizes, np.uint64)
+
+
 class Tables:
     """Flattened, device-resident scan tables (one per compiled rule set).
 
@@ -359,6 +378,53 @@ class Scanner:
         if out.size:
             ctypes.memmove(out.ctypes.data, rec, out.size * 16)
         return out, offsets
+
+    # -- batches of buffers scattered in device memory --------------------------
+    def batch_gather(self, d_arena: int, arena_size: int, starts, ptrs, sizes):
+        """Pack device buffers (``ptrs[k]``, ``sizes[k]`` bytes, any alignment) into
+        the device arena at ``d_arena``: buffer k at starts[k], every other byte
+        of [0, arena_size) zero (yr_amd_batch_gather; asynchronous)."""
+        st = _arr(starts, np.uint64).reshape(-1)
+        pt = _arr(ptrs, np.uint64).reshape(-1)
+        sz = _arr(sizes, np.uint64).reshape(-1)
+        if not st.size == pt.size == sz.size:
+            raise ValueError("starts, ptrs and sizes differ in length")
+        p = lambda a: a.ctypes.data_as(_lib._u64p) if a.size else None   # noqa: E731
+        _lib.check("yr_amd_batch_gather", _lib.lib().yr_amd_batch_gather(
+            self._h, ctypes.c_void_p(d_arena or None), arena_size, p(st), p(pt), p(sz), st.size))
+
+    def scan_batch_gather_device(self, ptrs, sizes):
+        """Batch scan of device buffers wherever they lie: packed into the
+        scanner's own arena and scanned (yr_amd_scan_batch_gather_device;
+        asynchronous).  Results: batch_result, verify_batch_device.  The buffers
+        must stay unchanged until batch_result has returned."""
+        pt = _arr(ptrs, np.uint64).reshape(-1)
+        sz = _arr(sizes, np.uint64).reshape(-1)
+        if pt.size != sz.size:
+            raise ValueError("ptrs and sizes differ in length")
+        p = lambda a: a.ctypes.data_as(_lib._u64p) if a.size else None   # noqa: E731
+        _lib.check("yr_amd_scan_batch_gather_device", _lib.lib().yr_amd_scan_batch_gather_device(
+            self._h, p(pt), p(sz), pt.size))
+        self._batch_n = pt.size
+
+    def batch_candidates_device(self, buffers):
+        """batch_candidates for buffers in device memory: each a ``(ptr, size)``
+        pair or an object with data_ptr(), numel(), element_size() and
+        is_contiguous() (a torch uint8 tensor on the scanner's device, or a
+        slice of one).  One gather and one scan for all of them."""
+        ptrs, sizes = _device_buffers(buffers)
+        self.scan_batch_gather_device(ptrs, sizes)
+        return self.batch_result()
+
+    def batch_verify_calls_device(self, buffers, bases=None):
+        """batch_verify_calls for buffers in device memory (see
+        batch_candidates_device): (records, offsets), copied to the host."""
+        ptrs, sizes = _device_buffers(buffers)
+        if bases is not None and _arr(bases, np.uint64).size != ptrs.size:
+            raise ValueError("one base per buffer")
+        self.scan_batch_gather_device(ptrs, sizes)
+        self.batch_result()
+        return self.verify_batch_device(bases)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

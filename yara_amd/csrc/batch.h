@@ -46,4 +46,18 @@ hipError_t launch_verify_batch(const VerifyParams& p, const BatchView& b, int pa
 hipError_t launch_batch_rec_offsets(const VerifyParams& p, const uint64_t* cand_off, uint32_t n,
                                     uint64_t* rec_off, hipStream_t s);
 
+constexpr uint32_t kGatherChunk = 512;   // arena granules (16 bytes) per wave and step: 8 KiB
+
+// Packing an arena from buffers scattered in device memory (gather.hip).
+struct GatherParams {
+  uint8_t* arena;              // 16-byte aligned; [0, arena_size) is written, nothing else
+  uint64_t arena_size;
+  const uint64_t* starts;      // [n] ascending, 16-byte aligned, buffers not overlapping
+  const uint64_t* sizes;       // [n]
+  const uint64_t* ptrs;        // [n] device addresses of the buffers, any alignment
+  uint32_t n;
+};
+
+hipError_t launch_batch_gather(const GatherParams& p, hipStream_t s);
+
 }  // namespace yamd

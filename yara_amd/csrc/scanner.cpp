@@ -226,6 +226,14 @@ struct yr_amd_scanner {
   std::vector<uint64_t> h_bstarts, h_bsizes, h_bases, h_cand_off, h_rec_off;
   uint8_t* h_arena = nullptr;           // pinned staging of yr_amd_scan_batch_verified
   size_t h_arena_cap = 0;
+  // yr_amd_batch_gather: its own table, [3 * n]: starts, sizes, buffer addresses
+  // (not a column of d_bstarts: a gather into a caller's arena may run, with
+  // another n, between a batch scan and its yr_amd_verify_batch_device)
+  uint64_t* d_gather = nullptr;
+  size_t gather_cap = 0;
+  std::vector<uint64_t> h_gather;
+  hipEvent_t ev_gather = nullptr;       // behind the table's upload: h_gather may be rewritten
+  bool gather_queued = false;
 };
 
 static_assert(sizeof(VerifyRec) == sizeof(yr_amd_verify_rec), "record layout");
@@ -466,7 +474,8 @@ int yr_amd_scanner_create(yr_amd_tables* tables, void* stream, yr_amd_scanner** 
       hipHostGetDevicePointer((void**)&s->d_hsum, s->h_summary, 0) != hipSuccess ||
       hipMalloc((void**)&s->d_summary, 2 * sizeof(uint64_t)) != hipSuccess ||
       hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&s->ev_counted, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&s->ev_counted, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&s->ev_gather, hipEventDisableTiming) != hipSuccess) {
     yr_amd_scanner_destroy(s);
     return YR_AMD_INTERNAL_FATAL_ERROR;
   }
@@ -487,7 +496,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_vchunk, (void*)s->d_seg_base,
                   (void*)s->d_seg_next, (void*)s->d_trace_T, (void*)s->d_trace_M,
                   (void*)s->d_bstarts, (void*)s->d_boff, (void*)s->d_btmp, (void*)s->d_bpos,
-                  (void*)s->d_bunit, (void*)s->d_bunit_off})
+                  (void*)s->d_bunit, (void*)s->d_bunit_off, (void*)s->d_gather})
     if (p) (void)hipFree(p);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
   if (s->h_summary) (void)hipHostFree(s->h_summary);
@@ -496,6 +505,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
   if (s->ev_compact) (void)hipEventDestroy(s->ev_compact);
   if (s->ev_done) (void)hipEventDestroy(s->ev_done);
   if (s->ev_counted) (void)hipEventDestroy(s->ev_counted);
+  if (s->ev_gather) (void)hipEventDestroy(s->ev_gather);
   if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
   return YR_AMD_SUCCESS;
@@ -1631,22 +1641,32 @@ int yr_amd_batch_layout(const uint64_t* sizes, uint64_t n, uint64_t* starts, uin
   return YR_AMD_SUCCESS;
 }
 
-int yr_amd_scan_batch_device(yr_amd_scanner* s, const uint8_t* d_arena, uint64_t arena_size,
-                             const uint64_t* starts, const uint64_t* sizes, uint64_t n) {
-  if (s == nullptr || n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (starts == nullptr || sizes == nullptr)))
-    return YR_AMD_INVALID_ARGUMENT;
+extern "C++" {
+namespace {
+// What every call that takes an arena and its layout requires of them.
+bool batch_arena_ok(const uint8_t* d_arena, uint64_t arena_size, const uint64_t* starts,
+                    const uint64_t* sizes, uint64_t n) {
+  if (n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (starts == nullptr || sizes == nullptr))) return false;
   // (an arena of arena_size bytes has at most arena_size + 1 candidates, and
   // records index candidates in 32 bits)
-  if (arena_size >= YR_AMD_VERIFY_MAX_CANDIDATES) return YR_AMD_INVALID_ARGUMENT;
-  if ((((uintptr_t)d_arena) & 15) != 0 || (d_arena == nullptr && arena_size > 0))
-    return YR_AMD_INVALID_ARGUMENT;
+  if (arena_size >= YR_AMD_VERIFY_MAX_CANDIDATES) return false;
+  if ((((uintptr_t)d_arena) & 15) != 0 || (d_arena == nullptr && arena_size > 0)) return false;
   uint64_t prev_end = 0;
   for (uint64_t k = 0; k < n; ++k) {
     if ((starts[k] & 15) != 0 || starts[k] < prev_end || sizes[k] > arena_size ||
         starts[k] > arena_size - sizes[k])
-      return YR_AMD_INVALID_ARGUMENT;
+      return false;
     prev_end = starts[k] + sizes[k];
   }
+  return true;
+}
+}  // namespace
+}  // extern "C++"
+
+int yr_amd_scan_batch_device(yr_amd_scanner* s, const uint8_t* d_arena, uint64_t arena_size,
+                             const uint64_t* starts, const uint64_t* sizes, uint64_t n) {
+  if (s == nullptr || !batch_arena_ok(d_arena, arena_size, starts, sizes, n))
+    return YR_AMD_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(s->tables->device));
   s->h_bstarts.assign(starts, starts + n);
   s->h_bsizes.assign(sizes, sizes + n);
@@ -1860,6 +1880,66 @@ int yr_amd_scan_batch_verified(yr_amd_scanner* s, const uint8_t* const* data, co
   if (records) *records = s->h_vrec.data();
   if (rec_off) *rec_off = off;
   return YR_AMD_SUCCESS;
+}
+
+// ---- Batches of buffers scattered in device memory: pack, then the arena path ----
+
+int yr_amd_batch_gather(yr_amd_scanner* s, uint8_t* d_arena, uint64_t arena_size,
+                        const uint64_t* starts, const uint8_t* const* d_buffers,
+                        const uint64_t* sizes, uint64_t n) {
+  if (s == nullptr || !batch_arena_ok(d_arena, arena_size, starts, sizes, n) ||
+      (n > 0 && d_buffers == nullptr))
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint64_t k = 0; k < n; ++k)
+    if (d_buffers[k] == nullptr && sizes[k] > 0) return YR_AMD_INVALID_ARGUMENT;
+  if (arena_size == 0) return YR_AMD_SUCCESS;
+  HIP_TRY(hipSetDevice(s->tables->device));
+  if (s->gather_queued) HIP_TRY(hipEventSynchronize(s->ev_gather));   // (the last upload has read h_gather)
+  s->gather_queued = false;
+  s->h_gather.resize(3 * (size_t)n);
+  for (uint64_t k = 0; k < n; ++k) {
+    s->h_gather[k] = starts[k];
+    s->h_gather[n + k] = sizes[k];
+    s->h_gather[2 * n + k] = (uint64_t)(uintptr_t)d_buffers[k];
+  }
+  int r = grow(s->d_gather, s->gather_cap, 3 * (size_t)n);
+  if (r) return r;
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(s->d_gather, s->h_gather.data(), 3 * n * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipEventRecord(s->ev_gather, s->stream));
+    s->gather_queued = true;
+  }
+  GatherParams g{};
+  g.arena = d_arena;
+  g.arena_size = arena_size;
+  g.starts = s->d_gather;
+  g.sizes = s->d_gather + n;
+  g.ptrs = s->d_gather + 2 * n;
+  g.n = (uint32_t)n;
+  HIP_TRY(launch_batch_gather(g, s->stream));
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_batch_gather_device(yr_amd_scanner* s, const uint8_t* const* d_buffers,
+                                    const uint64_t* sizes, uint64_t n) {
+  if (s == nullptr || n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (d_buffers == nullptr || sizes == nullptr)))
+    return YR_AMD_INVALID_ARGUMENT;
+  std::vector<uint64_t> st(n);
+  uint64_t arena = 0;
+  int r = yr_amd_batch_layout(sizes, n, st.data(), &arena);
+  if (r) return r;
+  if (arena >= YR_AMD_VERIFY_MAX_CANDIDATES) return YR_AMD_INVALID_ARGUMENT;
+  for (uint64_t k = 0; k < n; ++k)
+    if (d_buffers[k] == nullptr && sizes[k] > 0) return YR_AMD_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(s->tables->device));
+  // the scanner's own arena: the block workspace, in whole 16-byte granules
+  // (the gather itself writes no byte at or beyond `arena`)
+  r = grow(s->d_block, s->d_block_cap, std::max<size_t>((arena + 15) & ~15ull, 16));
+  if (r) return r;
+  r = yr_amd_batch_gather(s, s->d_block, arena, st.data(), d_buffers, sizes, n);
+  if (r) return r;
+  return yr_amd_scan_batch_device(s, s->d_block, arena, st.data(), sizes, n);
 }
 
 int yr_amd_trace_walk(yr_amd_scanner* s, const uint8_t* d_data, size_t size, uint64_t data_base,
