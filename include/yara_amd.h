@@ -435,6 +435,123 @@ int yr_amd_scan_block_verified(
     uint64_t* count);
 
 /*
+ * ---- Final matches of literal strings on the device ----
+ *
+ * What yr_amd_verify_device returns are calls the host still owes to
+ * yr_scan_verify_match.  For a FINAL string that call has only one outcome: a
+ * string is final when its flags have STRING_FLAGS_LITERAL (0x400) and none of
+ * STRING_FLAGS_CHAIN_PART (0x2000), STRING_FLAGS_BASE64 (0x200000),
+ * STRING_FLAGS_BASE64_WIDE (0x400000).  A kept call of such a string goes from
+ * _yr_scan_verify_literal_match through _yr_scan_match_callback straight to
+ * _yr_scan_add_match_to_list (scan.c:707-757): the call is a match.  The match
+ * stage turns those records into the YR_MATCH values libyara would hold, so a
+ * caller with a compiled rules file and no libyara gets "which string matched
+ * where" for its literal strings; regexp, hex, chain-part and base64 strings
+ * stay calls for a host verifier.
+ *
+ * out[k] = 1 iff string k is final.  Host code: works on host-only tables too.
+ * YR_AMD_INVALID_ARGUMENT without string records (yr_amd_tables_set_strings,
+ * or yr_amd_tables_set_string_flags on host-only tables) and when n_strings
+ * is not the tables' string count.
+ */
+int yr_amd_tables_final_strings(const yr_amd_tables* tables, uint8_t* out, uint32_t n_strings);
+
+/*
+ * Host-only tables (device = -1) cannot carry device strings
+ * (yr_amd_tables_set_strings refuses them); this attaches the part of the
+ * string records that host-only queries read -- YR_STRING.flags, indexed like
+ * rules->strings_table -- once.  YR_AMD_INVALID_ARGUMENT on device tables.
+ * yr_amd_tables_load_yarc with device = -1 attaches them itself.
+ */
+int yr_amd_tables_set_string_flags(yr_amd_tables* tables, const uint32_t* flags, uint32_t n_strings);
+
+/*
+ * The number of string records attached (by either call above, or by
+ * yr_amd_tables_load_yarc): the n_strings of yr_amd_tables_final_strings and
+ * the range of yr_amd_match_rec.string.  YR_AMD_INVALID_ARGUMENT without any.
+ */
+int yr_amd_tables_string_count(const yr_amd_tables* tables, uint32_t* n_strings);
+
+typedef struct
+{
+  uint64_t offset;      /* YR_MATCH.offset (block-local) */
+  uint32_t string;      /* YR_STRING.idx: index into yr_amd_tables_set_strings' array */
+  uint32_t length;      /* YR_MATCH.match_length */
+  uint32_t xor_key;     /* YR_MATCH.xor_key */
+  uint32_t pool_index;  /* the call that made it (first in call order) */
+} yr_amd_match_rec;     /* 24 bytes */
+
+/*
+ * The matches of the final strings in the last completed single-block scan
+ * (yr_amd_scan_device or yr_amd_scan_window, then yr_amd_scan_device_result):
+ * runs yr_amd_verify_device (same preconditions, same data_base) and then, on
+ * the scanner's stream, splits its records.
+ *
+ * *d_rest / *n_rest: the records whose string is not final, in their original
+ * order with every field unchanged -- the calls the host still owes to
+ * yr_scan_verify_match.  After yr_amd_scan_window a record of a final string
+ * whose bytes are not all in the window (the bounds yr_amd_verify_device keeps
+ * an undecided call by) is in the rest too; with the tables' verify halos, and
+ * on whole-block scans, that never happens.
+ *
+ * *d_matches / *n_matches: one entry per distinct (string, offset) among the
+ * other records, ascending by (string, offset) -- the order of libyara's
+ * per-string match lists (scan.c:290-352).  Of several calls with one (string,
+ * offset) the first in record order supplies length, xor_key and pool_index,
+ * as _yr_scan_add_match_to_list with replace_if_exists == 0 keeps the first.
+ * length and xor_key are forward_matches and xor_key of
+ * _yr_scan_verify_literal_match (scan.c:907-972): STRING_FLAGS_FITS_IN_ATOM
+ * gives the call's backtrack; else the ascii form gives the string's length,
+ * else the wide form twice that, else for an xor string without nocase the
+ * wide xor form and then the plain xor form, with xor_key = data[offset] ^
+ * string[0] (0 on every other path).
+ *
+ * YR_MAX_STRING_MATCHES (limits.h) is NOT applied: libyara stops adding to a
+ * string's list at that count and fails the scan with
+ * ERROR_TOO_MANY_MATCHES, which depends on the host's state in call order
+ * (earlier blocks included).  A caller that needs the cap counts per string.
+ *
+ * Both are DEVICE pointers owned by the scanner, valid until its next verify
+ * or match call.  Synchronous.  YR_AMD_INVALID_ARGUMENT: everything
+ * yr_amd_verify_device refuses, no completed scan, a batch scan (its key would
+ * need the buffer index), tables with yr_amd_tables_set_profiling enabled
+ * (count-only records are no calls), more than YR_AMD_MATCH_MAX_RECORDS
+ * records, and a block of more than YR_AMD_MATCH_MAX_BLOCK bytes: the stage
+ * keys a match by its offset in 32 bits, and offsets are positions of the
+ * block -- after yr_amd_scan_window too, whatever the window's size, so it is
+ * the block_size given to the scan that counts.  (yr_amd_verify_device bounds
+ * the candidate stream, not the block: it accepts such blocks, and their
+ * records are verified by the host as before.)  Cut larger inputs into blocks
+ * and merge (yara_amd.merge_matches).
+ */
+#define YR_AMD_MATCH_MAX_RECORDS 0x7FFFFFFFull
+#define YR_AMD_MATCH_MAX_BLOCK 0x100000000ull
+int yr_amd_match_device(
+    yr_amd_scanner* scanner,
+    uint64_t data_base,
+    const yr_amd_match_rec** d_matches,
+    uint64_t* n_matches,
+    const yr_amd_verify_rec** d_rest,
+    uint64_t* n_rest);
+
+/*
+ * Host-block convenience: H2D, scan, match stage, D2H.  *matches / *rest are
+ * host arrays owned by the scanner (valid until its next call).  A block of
+ * more than YR_AMD_MATCH_MAX_BLOCK bytes: YR_AMD_INVALID_ARGUMENT.  The blocks of
+ * one scan merge as libyara's lists do -- by base + offset, the earlier block
+ * winning (yara_amd.merge_matches).
+ */
+int yr_amd_scan_block_matches(
+    yr_amd_scanner* scanner,
+    const uint8_t* data,
+    size_t size,
+    uint64_t data_base,
+    const yr_amd_match_rec** matches,
+    uint64_t* n_matches,
+    const yr_amd_verify_rec** rest,
+    uint64_t* n_rest);
+
+/*
  * ---- Batched scans: many independent buffers in one launch ----
  *
  * Every call above takes one block and pays its fixed cost -- a scan launch in

@@ -24,7 +24,7 @@ from ._lib import (CALLBACK_ERROR, COULD_NOT_MAP_FILE, INSUFFICIENT_MEMORY,  # n
                    YaraAmdError)
 
 __all__ = ["Tables", "Scanner", "Pipeline", "replay", "fill_xorshift64", "version",
-           "batch_layout", "YaraAmdError"]
+           "batch_layout", "merge_matches", "YaraAmdError"]
 
 
 def _arr(a, dt):
@@ -120,7 +120,10 @@ class Tables:
         z = np.load(path)
         t = cls(z["T"], z["M"], z["pool_next"], z["pool_backtrack"], device=device)
         t.pool_string = z["pool_string"] if "pool_string" in z else None
-        if strings:
+        if strings and device < 0:
+            # host-only tables carry no device strings: the flags alone
+            t.set_string_flags(z["str_flags"])
+        elif strings:
             offs = z["str_offsets"]
             t.set_strings(z["pool_string"], z["str_flags"], np.diff(offs), z["str_fixed_offset"],
                           z["str_bytes"], offs[:-1])
@@ -159,6 +162,31 @@ class Tables:
         _lib.check("yr_amd_tables_set_strings", _lib.lib().yr_amd_tables_set_strings(
             self._h, ps.ctypes.data_as(_lib._u32p), self._ps.size, recs, n,
             self._blob.ctypes.data_as(_lib._u8p), len(blob), self._lower.ctypes.data_as(_lib._u8p)))
+
+    def set_string_flags(self, flags):
+        """Host-only tables: attach the strings' YR_STRING.flags
+        (yr_amd_tables_set_string_flags), all that final_strings reads."""
+        fl = _arr(flags, np.uint32).reshape(-1)
+        _lib.check("yr_amd_tables_set_string_flags", _lib.lib().yr_amd_tables_set_string_flags(
+            self._h, fl.ctypes.data_as(_lib._u32p) if fl.size else None, fl.size))
+
+    def string_count(self) -> int:
+        """Number of string records attached (yr_amd_tables_string_count)."""
+        n = ctypes.c_uint32()
+        _lib.check("yr_amd_tables_string_count",
+                   _lib.lib().yr_amd_tables_string_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def final_strings(self):
+        """bool[n_strings]: the strings whose kept verify calls are matches
+        (yr_amd_tables_final_strings) -- literal, not a chain part, not base64.
+        Scanner.string_matches settles these; calls on the others stay with a
+        host verifier."""
+        n = self.string_count()
+        out = np.zeros(max(n, 1), np.uint8)
+        _lib.check("yr_amd_tables_final_strings", _lib.lib().yr_amd_tables_final_strings(
+            self._h, out.ctypes.data_as(_lib._u8p), n))
+        return out[:n].astype(bool)
 
     def set_profiling(self, enable: bool = True):
         """Count-only records for libyara's profiling counters
@@ -293,6 +321,50 @@ class Scanner:
                    _lib.lib().yr_amd_verify_device(self._h, data_base, ctypes.byref(p),
                                                    ctypes.byref(cnt)))
         return p.value or 0, cnt.value
+
+    # -- final matches of literal strings --------------------------------------
+    def match_device(self, data_base: int = 0):
+        """(matches, rest) of the last completed device scan (yr_amd_match_device),
+        copied to the host: ``matches`` {offset, string, length, xor_key,
+        pool_index}, one per distinct (string, offset) of the final strings
+        (Tables.final_strings), ascending by (string, offset), block-local
+        offsets; ``rest`` {offset, pool_index, candidate}, the verify calls a
+        host verifier still has to make, in call order.  A block of more than
+        2^32 bytes (a window of one too) is refused: INVALID_ARGUMENT."""
+        from ._hip import memcpy
+        pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
+        nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check("yr_amd_match_device", _lib.lib().yr_amd_match_device(
+            self._h, data_base, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr),
+            ctypes.byref(nr)))
+        matches = np.zeros(nm.value, dtype=_lib.MATCH_REC_DTYPE)
+        rest = np.zeros(nr.value, dtype=_lib.VERIFY_REC_DTYPE)
+        if nm.value:
+            memcpy(matches.ctypes.data, pm.value, nm.value * 24, 2)
+        if nr.value:
+            memcpy(rest.ctypes.data, pr.value, nr.value * 16, 2)
+        return matches, rest
+
+    def string_matches(self, data: np.ndarray, data_base: int = 0):
+        """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
+        see match_device.  For the final strings ``matches`` is what stock
+        libyara's match lists hold after scanning this block alone; the blocks
+        of one scan merge with ``merge_matches``."""
+        d = _arr(data, np.uint8)
+        pm = ctypes.POINTER(_lib.MatchRec)()
+        pr = ctypes.POINTER(_lib.VerifyRec)()
+        nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+        dp = d.ctypes.data_as(_lib._u8p) if d.size else None
+        _lib.check("yr_amd_scan_block_matches", _lib.lib().yr_amd_scan_block_matches(
+            self._h, dp, d.size, data_base, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr),
+            ctypes.byref(nr)))
+        matches = np.zeros(nm.value, dtype=_lib.MATCH_REC_DTYPE)
+        rest = np.zeros(nr.value, dtype=_lib.VERIFY_REC_DTYPE)
+        if nm.value:
+            ctypes.memmove(matches.ctypes.data, pm, nm.value * 24)
+        if nr.value:
+            ctypes.memmove(rest.ctypes.data, pr, nr.value * 16)
+        return matches, rest
 
     # -- batches: N independent buffers, one scan, one pre-verification -------
     def scan_batch_device(self, d_ptr: int, arena_size: int, starts, sizes):
@@ -512,6 +584,31 @@ class Scanner:
             self.close()
         except Exception:
             pass
+
+
+def merge_matches(blocks):
+    """The match lists of one scan from its blocks' matches: ``blocks`` is a
+    list of ``(base, matches)`` in block order (Scanner.string_matches /
+    match_device results).  Returns one array with absolute offsets ``base +
+    offset``, ascending by (string, offset); of several matches with one
+    (string, absolute offset) -- blocks that overlap -- the first block's is
+    kept.  That is what libyara's per-string lists hold after the blocks:
+    _yr_scan_add_match_to_list (scan.c:290-352) compares base + offset and
+    discards a literal's second match at a place already present."""
+    parts = []
+    for base, m in blocks:
+        m = np.array(m, dtype=_lib.MATCH_REC_DTYPE)
+        m["offset"] += np.uint64(base)
+        parts.append(m)
+    if not parts:
+        return np.zeros(0, dtype=_lib.MATCH_REC_DTYPE)
+    allm = np.concatenate(parts)
+    # stable sort: equal (string, offset) stay in block order, the first wins
+    order = np.lexsort((allm["offset"], allm["string"]))
+    allm = allm[order]
+    keep = np.ones(allm.size, bool)
+    keep[1:] = (allm["string"][1:] != allm["string"][:-1]) | (allm["offset"][1:] != allm["offset"][:-1])
+    return allm[keep]
 
 
 def fill_xorshift64(d_ptr: int, n: int, seed: int, offset: int = 0, stream: int = 0):

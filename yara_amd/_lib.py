@@ -19,6 +19,7 @@ CALLBACK_ERROR = 28
 INVALID_ARGUMENT = 29
 INTERNAL_FATAL_ERROR = 31
 MAX_ATOM_LENGTH = 4
+MATCH_MAX_BLOCK = 1 << 32   # YR_AMD_MATCH_MAX_BLOCK
 
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u16p = ctypes.POINTER(ctypes.c_uint16)
@@ -64,7 +65,16 @@ class VerifyRec(ctypes.Structure):
                 ("candidate", ctypes.c_uint32)]
 
 
+class MatchRec(ctypes.Structure):
+    """yr_amd_match_rec (include/yara_amd.h)."""
+    _fields_ = [("offset", ctypes.c_uint64), ("string", ctypes.c_uint32),
+                ("length", ctypes.c_uint32), ("xor_key", ctypes.c_uint32),
+                ("pool_index", ctypes.c_uint32)]
+
+
 VERIFY_REC_DTYPE = [("offset", "<u8"), ("pool_index", "<u4"), ("candidate", "<u4")]
+MATCH_REC_DTYPE = [("offset", "<u8"), ("string", "<u4"), ("length", "<u4"), ("xor_key", "<u4"),
+                   ("pool_index", "<u4")]   # yr_amd_match_rec
 TRACE_REC_DTYPE = [("position", "<u8"), ("state", "<u4"), ("match", "<u4")]   # yr_amd_trace_rec
 
 # name -> (restype, argtypes); every function include/yara_amd.h declares
@@ -101,6 +111,17 @@ PROTOTYPES = {
     "yr_amd_re_code_extent": (_int, [_u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]),
     "yr_amd_verify_device": (_int, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp),
                                     ctypes.POINTER(ctypes.c_uint64)]),
+    "yr_amd_tables_final_strings": (_int, [_vp, _u8p, ctypes.c_uint32]),
+    "yr_amd_tables_set_string_flags": (_int, [_vp, _u32p, ctypes.c_uint32]),
+    "yr_amd_tables_string_count": (_int, [_vp, _u32p]),
+    "yr_amd_match_device": (_int, [_vp, ctypes.c_uint64, ctypes.POINTER(_vp),
+                                   ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(ctypes.c_uint64)]),
+    "yr_amd_scan_block_matches": (_int, [_vp, _u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                         ctypes.POINTER(ctypes.POINTER(MatchRec)),
+                                         ctypes.POINTER(ctypes.c_uint64),
+                                         ctypes.POINTER(ctypes.POINTER(VerifyRec)),
+                                         ctypes.POINTER(ctypes.c_uint64)]),
     "yr_amd_pipeline_create": (_int, [_vp, ctypes.c_uint32, ctypes.POINTER(_vp)]),
     "yr_amd_pipeline_destroy": (_int, [_vp]),
     "yr_amd_pipeline_submit": (_int, [_vp, _u8p, ctypes.c_size_t, ctypes.c_uint64]),

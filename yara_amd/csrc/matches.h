@@ -1,0 +1,78 @@
+// Device data of the final-match stage for literal strings (matches.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "verify.h"
+
+namespace yamd {
+
+constexpr uint32_t kStrChainPart = 0x2000;   // STRING_FLAGS_CHAIN_PART (types.h:66-88)
+
+// A FINAL string: a kept call of it goes from _yr_scan_verify_literal_match
+// through _yr_scan_match_callback straight to _yr_scan_add_match_to_list
+// (scan.c:707-757) -- the call IS a match.  Literal, not a chain part (those
+// are assembled by _yr_scan_verify_chained_string_match), not base64 (whose
+// comparison the device does not restate).
+__host__ __device__ inline bool string_is_final(uint32_t flags) {
+  return (flags & kStrLiteral) != 0 && (flags & (kStrChainPart | kStrBase64Any)) == 0;
+}
+
+// Same layout as yr_amd_match_rec (include/yara_amd.h).
+struct MatchRec {
+  uint64_t offset;
+  uint32_t string, length, xor_key, pool_index;
+};
+static_assert(sizeof(MatchRec) == 24, "match record layout");
+
+// What the classify pass measured of a record: YR_MATCH.match_length, xor_key.
+struct MatchMeasure {
+  uint32_t length, xor_key;
+};
+
+struct MatchParams {
+  const uint8_t* data;          // block (position 0; only [win_lo, win_hi) is read)
+  uint64_t size;
+  uint64_t win_lo, win_hi;
+  const VerifyRec* recs;        // yr_amd_verify_device's records
+  uint64_t n;                   // (at most kMatchMaxRecords)
+  const DevPoolRec* pool;
+  const uint32_t* pool_string;  // [n_pool] YR_STRING.idx of the pool entry's string
+  uint32_t n_strings;           // a key's string field == n_strings: not a match (rest)
+  const uint8_t* str_bytes;
+  const uint8_t* lowercase;
+  uint64_t* keys;               // [n] string << 32 | offset, in record order
+  uint32_t* index;              // [n] record index (the sort's values)
+  MatchMeasure* meas;           // [n] by record
+  const uint64_t* sorted_keys;  // [n] after the stable sort
+  const uint32_t* sorted_index;
+  uint64_t* block_off;          // [verify_groups(n) + 1] per-wave counts -> offsets
+  uint64_t* chunk_off;          // [verify_chunks(n) + 1] (launch_block_offsets)
+  VerifyRec* rest;              // [n]
+  MatchRec* out;                // [n]
+};
+
+// Output slots and one dispatch's work-items are 32-bit counts.
+constexpr uint64_t kMatchMaxRecords = 0x7FFFFFFFull;
+
+// Classify + measure: keys, index, meas, and the rest records per wave into block_off.
+hipError_t launch_match_classify(const MatchParams& p, hipStream_t s);
+// The rest records, stably compacted (block_off / chunk_off scanned).
+hipError_t launch_match_rest(const MatchParams& p, hipStream_t s);
+// Stable radix sort of (keys[0], index[0]) by the key bits [0, lo_bits) and
+// [32, 32 + hi_bits), ping-pong between the two buffers of each pair:
+// *result = the buffer that holds the sorted arrays.  hist: [match_sort_hist(n)
+// + 1] and chunk: [verify_chunks(match_sort_hist(n) * kGroup) + 1] workspace,
+// total: one scratch word (device-writable).
+constexpr uint32_t kSortTile = 2048;   // items per wave
+inline uint64_t match_sort_tiles(uint64_t n) { return (n + kSortTile - 1) / kSortTile; }
+inline uint64_t match_sort_hist(uint64_t n) { return 256 * match_sort_tiles(n); }
+hipError_t match_sort(uint64_t* const keys[2], uint32_t* const index[2], uint64_t n, int lo_bits,
+                      int hi_bits, uint64_t* hist, uint64_t* chunk, uint64_t* total, hipStream_t s,
+                      int* result);
+// pass 0: distinct keys per wave into block_off; pass 1 (offsets scanned):
+// the first entry of every run of equal keys as a MatchRec.
+hipError_t launch_match_unique(const MatchParams& p, int pass, hipStream_t s);
+
+}  // namespace yamd

@@ -23,6 +23,7 @@
 #include "re_program.h"
 #include "verify.h"
 #include "batch.h"
+#include "matches.h"
 
 namespace yamd {
 hipError_t launch_scan(const ScanParams& p, int grid, hipStream_t s, int mode, hipEvent_t t0 = nullptr,
@@ -116,6 +117,8 @@ struct yr_amd_tables {
   uint8_t* d_re_code = nullptr;       // yr_amd_tables_set_re_code
   std::vector<DevPoolRec> h_pool;     // host copy of the records (set_re_code fills .re)
   std::vector<uint32_t> h_str_flags, h_pool_string;   // host copies (validation)
+  bool has_str_flags = false;         // yr_amd_tables_set_string_flags (host-only tables)
+  uint32_t* d_pool_string = nullptr;  // [n_pool] the entries' string indexes (matches.hip)
   uint64_t max_str_bytes = 0;     // max over strings of the bytes a comparison reads
 };
 
@@ -205,6 +208,28 @@ struct yr_amd_scanner {
   VerifyRec* d_vrec = nullptr;
   size_t vrec_cap = 0;
   std::vector<yr_amd_verify_rec> h_vrec;
+
+  // a single-block scan was started on this scanner (yr_amd_match_device)
+  bool scanned = false;
+  // match stage workspace (yr_amd_match_device; matches.h MatchParams)
+  uint64_t* d_mkeys = nullptr;          // [2 * cap]: keys in record order, sorted
+  uint32_t* d_mindex = nullptr;         // [2 * cap]: record indexes likewise
+  MatchMeasure* d_mmeas = nullptr;      // [cap]
+  VerifyRec* d_mrest = nullptr;         // [cap]
+  MatchRec* d_mout = nullptr;           // [cap]
+  size_t match_cap = 0;                 // records the five arrays above hold
+  uint64_t* d_mblock = nullptr;         // per-wave counts -> offsets
+  size_t mblock_cap = 0;
+  uint64_t* d_mchunk = nullptr;
+  size_t mchunk_cap = 0;
+  uint64_t* d_mhist = nullptr;          // the sort's digit histograms -> offsets
+  size_t mhist_cap = 0;
+  uint64_t* d_mhchunk = nullptr;
+  size_t mhchunk_cap = 0;
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch}
+  uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
+  std::vector<yr_amd_match_rec> h_match;
+  std::vector<yr_amd_verify_rec> h_mrest;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -404,7 +429,8 @@ int yr_amd_tables_create(const uint32_t* transition_table, const uint32_t* match
 int yr_amd_tables_destroy(yr_amd_tables* t) {
   if (t == nullptr) return YR_AMD_SUCCESS;
   for (void* p : {(void*)t->d_filter, (void*)t->d_exact, (void*)t->d_nodes, (void*)t->d_kc, (void*)t->d_pool,
-                  (void*)t->d_str_bytes, (void*)t->d_lowercase, (void*)t->d_re_code})
+                  (void*)t->d_str_bytes, (void*)t->d_lowercase, (void*)t->d_re_code,
+                  (void*)t->d_pool_string})
     if (p) (void)hipFree(p);
   delete t;
   return YR_AMD_SUCCESS;
@@ -496,8 +522,12 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_vchunk, (void*)s->d_seg_base,
                   (void*)s->d_seg_next, (void*)s->d_trace_T, (void*)s->d_trace_M,
                   (void*)s->d_bstarts, (void*)s->d_boff, (void*)s->d_btmp, (void*)s->d_bpos,
-                  (void*)s->d_bunit, (void*)s->d_bunit_off, (void*)s->d_gather})
+                  (void*)s->d_bunit, (void*)s->d_bunit_off, (void*)s->d_gather,
+                  (void*)s->d_mkeys, (void*)s->d_mindex, (void*)s->d_mmeas, (void*)s->d_mrest,
+                  (void*)s->d_mout, (void*)s->d_mblock, (void*)s->d_mchunk, (void*)s->d_mhist,
+                  (void*)s->d_mhchunk})
     if (p) (void)hipFree(p);
+  if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
   if (s->h_summary) (void)hipHostFree(s->h_summary);
   if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
@@ -617,6 +647,7 @@ int yr_amd_scan_window(yr_amd_scanner* s, const uint8_t* d_window, uint64_t wind
     return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_tables* t = s->tables;
   s->pending = true;
+  s->scanned = true;
   s->batch = false;
   s->batch_done = false;
   s->last_count = 0;
@@ -869,6 +900,7 @@ int yr_amd_tables_set_strings(yr_amd_tables* t, const uint32_t* pool_string, uin
     if (!r) r = upload(t->d_str_bytes, padded.data(), padded.size());
   }
   if (!r) r = upload(t->d_lowercase, lowercase, 256);
+  if (!r) r = upload(t->d_pool_string, pool_string, (size_t)n_pool);
   if (r) return r;   // partial uploads are freed with the tables
   t->h_pool_string.assign(pool_string, pool_string + n_pool);
   t->h_str_flags.resize(n_strings);
@@ -1622,6 +1654,202 @@ int yr_amd_scan_block_verified(yr_amd_scanner* s, const uint8_t* data, size_t si
   }
   if (records) *records = s->h_vrec.data();
   if (count) *count = n;
+  return YR_AMD_SUCCESS;
+}
+
+// ---- Final matches of literal strings (matches.hip) ----
+
+static_assert(sizeof(MatchRec) == sizeof(yr_amd_match_rec), "match record layout");
+
+int yr_amd_tables_set_string_flags(yr_amd_tables* t, const uint32_t* flags, uint32_t n_strings) {
+  if (t == nullptr || t->device >= 0 || t->has_str_flags || (n_strings > 0 && flags == nullptr))
+    return YR_AMD_INVALID_ARGUMENT;
+  t->h_str_flags.assign(flags, flags + n_strings);
+  t->has_str_flags = true;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_tables_final_strings(const yr_amd_tables* t, uint8_t* out, uint32_t n_strings) {
+  if (t == nullptr || !(t->has_strings || t->has_str_flags) || n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && out == nullptr))
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_strings; ++k) out[k] = string_is_final(t->h_str_flags[k]) ? 1 : 0;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_tables_string_count(const yr_amd_tables* t, uint32_t* n_strings) {
+  if (t == nullptr || n_strings == nullptr || !(t->has_strings || t->has_str_flags))
+    return YR_AMD_INVALID_ARGUMENT;
+  *n_strings = (uint32_t)t->h_str_flags.size();
+  return YR_AMD_SUCCESS;
+}
+
+extern "C++" {
+namespace {
+// The match stage's buffers grow geometrically, like the record buffer of
+// yr_amd_verify_device: record counts that creep upward reallocate O(log) times.
+template <typename T>
+int grow_geo(T*& p, size_t& cap, size_t need) {
+  if (need <= cap && p != nullptr) return YR_AMD_SUCCESS;
+  return grow(p, cap, std::max(need, 2 * cap));
+}
+
+// A fresh allocation of `need` elements in place of p, whatever p held.
+template <typename T>
+int reallocate(T*& p, size_t need) {
+  size_t cap = 0;   // (no capacity: grow frees p and allocates)
+  return grow(p, cap, need);
+}
+
+int ensure_match_workspace(yr_amd_scanner* s, uint64_t n) {
+  if (s->h_msum == nullptr) {
+    if (hipHostMalloc((void**)&s->h_msum, 3 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
+      s->h_msum = nullptr;
+      return YR_AMD_INSUFFICIENT_MEMORY;
+    }
+    if (hipHostGetDevicePointer((void**)&s->d_mhsum, s->h_msum, 0) != hipSuccess) {
+      // (both or neither: a later call must not find the host word without its device address)
+      (void)hipHostFree(s->h_msum);
+      s->h_msum = nullptr;
+      s->d_mhsum = nullptr;
+      return YR_AMD_INSUFFICIENT_MEMORY;
+    }
+  }
+  if (n > s->match_cap || s->d_mout == nullptr) {
+    // the five per-record arrays share one capacity, match_cap
+    const size_t cap = std::max<size_t>(n, 2 * s->match_cap);
+    int r = reallocate(s->d_mkeys, 2 * cap);
+    if (!r) r = reallocate(s->d_mindex, 2 * cap);
+    if (!r) r = reallocate(s->d_mmeas, cap);
+    if (!r) r = reallocate(s->d_mrest, cap);
+    if (!r) r = reallocate(s->d_mout, cap);
+    s->match_cap = r ? 0 : cap;
+    if (r) return r;
+  }
+  int r = grow_geo(s->d_mblock, s->mblock_cap, verify_groups(n) + 1);
+  if (!r) r = grow_geo(s->d_mchunk, s->mchunk_cap, verify_chunks(n) + 1);
+  const uint64_t hist = match_sort_hist(n);
+  if (!r) r = grow_geo(s->d_mhist, s->mhist_cap, hist + 1);
+  if (!r) r = grow_geo(s->d_mhchunk, s->mhchunk_cap, verify_chunks(hist * kGroup) + 1);
+  return r;
+}
+}  // namespace
+}  // extern "C++"
+
+int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_match_rec** d_matches,
+                        uint64_t* n_matches, const yr_amd_verify_rec** d_rest, uint64_t* n_rest) {
+  if (s == nullptr || s->pending || !s->scanned || s->batch || !s->tables->has_strings)
+    return YR_AMD_INVALID_ARGUMENT;
+  // (count-only records are no calls: they have no match meaning)
+  if (s->tables->profile) return YR_AMD_INVALID_ARGUMENT;
+  // The key holds an offset in 32 bits.  Offsets are positions of the BLOCK (a
+  // window's too), below its size -- and yr_amd_verify_device bounds the
+  // candidate count, not the size, so a larger block is refused here.
+  if (s->last.block_size > YR_AMD_MATCH_MAX_BLOCK) return YR_AMD_INVALID_ARGUMENT;
+  const yr_amd_tables* t = s->tables;
+  const yr_amd_verify_rec* d_rec = nullptr;
+  uint64_t n = 0;
+  int r = yr_amd_verify_device(s, data_base, &d_rec, &n);
+  if (r) return r;
+  if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
+  uint64_t nm = 0, nr = 0;
+  if (n > 0) {   // (no records: no kernel is launched)
+    r = ensure_match_workspace(s, n);
+    if (r) return r;
+    MatchParams p{};
+    p.data = s->last.data;
+    p.size = s->last.block_size;
+    p.win_lo = s->win_lo;
+    p.win_hi = s->win_hi;
+    p.recs = reinterpret_cast<const VerifyRec*>(d_rec);
+    p.n = n;
+    p.pool = t->d_pool;
+    p.pool_string = t->d_pool_string;
+    p.n_strings = (uint32_t)t->h_str_flags.size();
+    p.str_bytes = t->d_str_bytes;
+    p.lowercase = t->d_lowercase;
+    p.keys = s->d_mkeys;
+    p.index = s->d_mindex;
+    p.meas = s->d_mmeas;
+    p.block_off = s->d_mblock;
+    p.chunk_off = s->d_mchunk;
+    p.rest = s->d_mrest;
+    p.out = s->d_mout;
+    // the key's bits that vary: the offset's (below the block size), and the
+    // string field's up to the value n_strings itself (the rest records')
+    int lo_bits = 1, hi_bits = 1;
+    while (lo_bits < 32 && ((p.size - 1) >> lo_bits) != 0) ++lo_bits;
+    while (hi_bits < 32 && (p.n_strings >> hi_bits) != 0) ++hi_bits;
+    uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+    uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+    const KeptLists none{{0, 0, 0, 0}};
+    // classify -> the rest's offsets -> the rest; sort; distinct keys -> their
+    // offsets -> the matches; one wait
+    HIP_TRY(launch_match_classify(p, s->stream));
+    HIP_TRY(launch_block_offsets(p.block_off, p.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
+    HIP_TRY(launch_match_rest(p, s->stream));
+    int sorted = 0;
+    HIP_TRY(match_sort(keys, index, n, lo_bits, hi_bits, s->d_mhist, s->d_mhchunk, s->d_mhsum + 2,
+                       s->stream, &sorted));
+    p.sorted_keys = keys[sorted];
+    p.sorted_index = index[sorted];
+    HIP_TRY(launch_match_unique(p, 0, s->stream));
+    HIP_TRY(launch_block_offsets(p.block_off, p.chunk_off, n, s->d_mhsum + 1, nullptr, none,
+                                 s->stream));
+    HIP_TRY(launch_match_unique(p, 1, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    nr = s->h_msum[0];
+    nm = s->h_msum[1];
+    if (nr > n || nm > n - nr) return YR_AMD_INTERNAL_FATAL_ERROR;
+  }
+  if (debug_level() >= 1)
+    fprintf(stderr, "- %llu verify calls -> %llu matches, %llu calls left // yr_amd_match_device()\n",
+            (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
+  if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
+  if (n_matches) *n_matches = nm;
+  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(s->d_mrest);
+  if (n_rest) *n_rest = nr;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_block_matches(yr_amd_scanner* s, const uint8_t* data, size_t size,
+                              uint64_t data_base, const yr_amd_match_rec** matches,
+                              uint64_t* n_matches, const yr_amd_verify_rec** rest,
+                              uint64_t* n_rest) {
+  if (s == nullptr || (data == nullptr && size > 0)) return YR_AMD_INVALID_ARGUMENT;
+  if (!s->tables->has_strings || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;
+  if ((uint64_t)size > YR_AMD_MATCH_MAX_BLOCK) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
+  HIP_TRY(hipSetDevice(s->tables->device));
+  int rg = grow(s->d_block, s->d_block_cap, std::max<size_t>(size, 16));
+  if (rg) return rg;
+  if (size > 0 &&
+      hipMemcpyAsync(s->d_block, data, size, hipMemcpyHostToDevice, s->stream) != hipSuccess)
+    return YR_AMD_COULD_NOT_MAP_FILE;
+  // (a verified-only scan, as in yr_amd_scan_block_verified: the records are
+  // the same, and nothing but what they become leaves this call)
+  const bool was = s->verified_only;
+  s->verified_only = true;
+  int r = yr_amd_scan_device(s, s->d_block, size, 0, size);
+  if (!r) r = yr_amd_scan_device_result(s, nullptr, nullptr, nullptr);
+  s->verified_only = was;
+  const yr_amd_match_rec* d_m = nullptr;
+  const yr_amd_verify_rec* d_r = nullptr;
+  uint64_t nm = 0, nr = 0;
+  if (!r) r = yr_amd_match_device(s, data_base, &d_m, &nm, &d_r, &nr);
+  if (r) return r;
+  s->h_match.resize(nm);
+  s->h_mrest.resize(nr);
+  if (nm > 0)
+    HIP_TRY(hipMemcpyAsync(s->h_match.data(), d_m, nm * sizeof(yr_amd_match_rec),
+                           hipMemcpyDeviceToHost, s->stream));
+  if (nr > 0)
+    HIP_TRY(hipMemcpyAsync(s->h_mrest.data(), d_r, nr * sizeof(yr_amd_verify_rec),
+                           hipMemcpyDeviceToHost, s->stream));
+  if (nm > 0 || nr > 0) HIP_TRY(hipStreamSynchronize(s->stream));
+  if (matches) *matches = s->h_match.data();
+  if (n_matches) *n_matches = nm;
+  if (rest) *rest = s->h_mrest.data();
+  if (n_rest) *n_rest = nr;
   return YR_AMD_SUCCESS;
 }
 

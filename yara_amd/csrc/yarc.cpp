@@ -234,6 +234,15 @@ extern "C" int yr_amd_tables_load_yarc(const uint8_t* file, size_t file_size, in
       yr_amd_tables_destroy(t);
       return r;
     }
+  } else {
+    // host-only tables: the strings' flags, for yr_amd_tables_final_strings
+    std::vector<uint32_t> flags(n_strings);
+    for (uint32_t k = 0; k < n_strings; ++k) flags[k] = st[k].flags;
+    r = yr_amd_tables_set_string_flags(t, flags.data(), n_strings);
+    if (r) {
+      yr_amd_tables_destroy(t);
+      return r;
+    }
   }
   *tables = t;
   return YR_AMD_SUCCESS;
