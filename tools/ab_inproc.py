@@ -33,8 +33,9 @@ _vp = ctypes.c_void_p
 
 
 def load(name):
-    name = name.split(":")[0]   # (a ":vo" suffix: that variant's scanner in verified-only mode)
+    name = name.split("@")[0].split(":")[0]   # (a ":vo" suffix: that variant's scanner in verified-only mode)
     path = (os.path.join(REPO, "yara_amd", "libyara_amd.so") if name == "base"
+            else os.path.join(REPO, "yara_amd", "_diag", "libyara_amd.so") if name == "diag"
             else os.path.join(REPO, "yara_amd", "_variants", name + ".so"))
     L = ctypes.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | os.RTLD_NOW)
     for fn, args in (("yr_amd_tables_create", [_vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
@@ -114,10 +115,16 @@ def main():
             code = code if code.size else np.zeros(1, np.uint8)
         keep += [recs, ps, blob, lower, re_arrs]
     scanners = []
-    for L in libs:
+    for L, name in zip(libs, names):
         t, s = _vp(), _vp()
+        # "diag@YAMD_PAIR_FILTER=1": the diagnostic build with that switch set while
+        # its tables are made (tables.cpp reads the filter switches there)
+        sw = dict(kv.split("=", 1) for kv in name.split(":")[0].split("@")[1:])
+        os.environ.update(sw)
         assert L.yr_amd_tables_create(T.ctypes.data, M.ctypes.data, T.size, nx.ctypes.data,
                                       bt.ctypes.data, nx.size, 0, ctypes.byref(t)) == 0
+        for k in sw:
+            del os.environ[k]
         if a.strings:
             assert L.yr_amd_tables_set_strings(t, ps.ctypes.data, int(z["pool_string"].size), ctypes.addressof(recs),
                                                n_str, blob.ctypes.data, blob_n, lower.ctypes.data) == 0
@@ -163,6 +170,7 @@ def main():
     verms = {v: [] for v in names}
     counts = {}
     ratios = {v: [] for v in names}
+    rmed = {v: [] for v in names}
     for r in range(a.rounds):
         order = list(range(len(names))) if r % 2 == 0 else list(reversed(range(len(names))))
         med = {}
@@ -178,6 +186,18 @@ def main():
             med[names[i]] = statistics.median(ks)
         for v in names:
             ratios[v].append(med[v] / med[names[0]])
+            rmed[v].append(med[v])
+
+    def spread_pct(xs):   # interquartile range of the per-round medians, % of their median
+        q = statistics.quantiles(xs, n=4)
+        return round(100.0 * (q[2] - q[0]) / statistics.median(xs), 3)
+
+    def quarters_pct(xs):
+        # the call cut into four consecutive quarters, each one's median, (max - min) / median in %:
+        # the in-call spread of a build, as bench.py alternated four times per build gives it
+        n = len(xs) // 4
+        m = [statistics.median(xs[i * n:(i + 1) * n]) for i in range(4)]
+        return round(100.0 * (max(m) - min(m)) / statistics.median(m), 3)
     out = {"rules": a.rules, "bytes": n, "rounds": a.rounds, "reps": a.reps, "strings": a.strings,
            "variants": {}}
     for v in names:
@@ -185,6 +205,8 @@ def main():
                               "kernel_min_ms": round(min(kern[v]), 4),
                               "scan_median_ms": round(statistics.median(scanms[v]), 4),
                               "ratio_to_first_median": round(statistics.median(ratios[v]), 4),
+                              "round_median_spread_pct": spread_pct(rmed[v]) if a.rounds >= 4 else None,
+                              "quarter_median_spread_pct": quarters_pct(kern[v]) if a.rounds >= 4 else None,
                               **({"verify_median_ms": round(statistics.median(verms[v]), 4),
                                   "step_wall_median_ms": round(statistics.median(wall[v]), 4)} if a.verify else {}),
                               "candidates": counts[v]}

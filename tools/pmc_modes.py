@@ -3,6 +3,18 @@ of the scan kernel averaged over the last `reps` launches of each pass (the
 earlier launches are tools/ablate.py's mode-0 clock warm-up).
 
     python tools/pmc_modes.py gpurun_out/pmc_<tag> [--reps 4] [--out file.json]
+    python tools/pmc_modes.py profiles/<earlier summary>.json --out file.json
+                              (derive again from a summary's recorded counters)
+
+GRBM_GUI_ACTIVE arrives summed over the chip's 8 XCDs, so the kernel's cycles
+are a eighth of it; SQ_ACTIVE_INST_* count quad-cycles (4 cycles each), summed
+over the CUs.  The busy fractions are fractions of the kernel's cycles: VALU
+per SIMD, LDS per CU.  (Until profiles/r06_pmc_detail_final.json the divisor
+was the 8-XCD sum times 4, which made the VALU fraction read as 3 %.)
+valu_busy_frac is the counter's booking of one quad-cycle per instruction; the
+issue costs measured on gfx950 are 1.9 cycles for a VOP2 and 3.3 for a
+VOP3 / SDWA form (profiles/s1_valu_rates.json), so the pipe's own occupancy is
+lower.
 """
 import argparse
 import collections
@@ -18,8 +30,12 @@ def main():
     ap.add_argument("dir")
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--out")
+    ap.add_argument("--xcds", type=int, default=8)
     a = ap.parse_args()
     res = collections.defaultdict(dict)
+    if a.dir.endswith(".json"):
+        for mode, rec in json.load(open(a.dir)).items():
+            res[int(mode)] = rec["counters"]
     for path in sorted(glob.glob(os.path.join(a.dir, "m*_p*", "**", "*counter_collection.csv"),
                                  recursive=True)):
         mode = int(re.search(r"/m(\d+)_p\d+", path).group(1))
@@ -33,12 +49,12 @@ def main():
             res[mode][name] = sum(last) / len(last)
     out = {}
     for mode, c in sorted(res.items()):
-        g = c.get("GRBM_GUI_ACTIVE", 0)
+        g = c.get("GRBM_GUI_ACTIVE", 0) / a.xcds   # the kernel's cycles
         der = {}
         if g:
-            cus = 256
-            der["kernel_us_at_clock"] = None
-            der["valu_busy_frac"] = c.get("SQ_ACTIVE_INST_VALU", 0) / (g * cus * 4)
+            cus, simds = 256, 4
+            der["kernel_cycles"] = g
+            der["valu_busy_frac"] = c.get("SQ_ACTIVE_INST_VALU", 0) * 4 / (g * cus * simds)
             der["lds_idx_active_frac"] = c.get("SQ_LDS_IDX_ACTIVE", 0) / (g * cus)
             der["lds_conflict_frac_of_active"] = (c.get("SQ_LDS_BANK_CONFLICT", 0) /
                                                   max(1.0, c.get("SQ_LDS_IDX_ACTIVE", 0)))

@@ -160,6 +160,89 @@ __device__ __forceinline__ uint32_t pair_window(const uint32_t (&S)[6], uint32_t
   return (o & 3) == 0 ? S[o >> 2] : __builtin_amdgcn_alignbyte(S[(o >> 2) + 1], S[o >> 2], 2);
 }
 
+// Stage 1's shift amounts without instructions that only move bits to where a
+// shift reads them.  The shifter reads the low 5 bits of its amount, so an
+// SDWA WORD_1 select on the amount operand supplies bits 16..20 of a register
+// as they lie.  An SDWA shift issues in 3.3 cycles against 1.9 of the VOP2
+// form (profiles/s1_valu_rates.json), so a select pays where it saves more
+// than one VOP2 per shift it converts.  Three pieces, each with its own
+// switch for A/B builds (profiles/s1_fields_ab.json):
+//   YAMD_S1_ALIGNBIT  an even pair 2m (window x = bits 16..47 of S[m+1]:S[m])
+//                     never forms x: its block address is one v_alignbit_b32
+//                     and a mask, its field x[0..4] is S[m].WORD_1 (on)
+//   YAMD_S1_LFIELD    one S[m] >> 5 serves x[5..9] of the odd pair 2m-1 (low
+//                     bits) and of the even pair 2m (WORD_1): 3 VOP2 fewer for
+//                     4 shifts made SDWA, config C +0.5 % -- off
+//   YAMD_S1_RFIELD    one y2 >> 5 of the v_perm that holds the right windows
+//                     of pairs 2m, 2m+1 serves both (low bits, WORD_1) (on)
+#ifndef YAMD_S1_ALIGNBIT
+#define YAMD_S1_ALIGNBIT 1
+#endif
+#ifndef YAMD_S1_LFIELD
+#define YAMD_S1_LFIELD 0
+#endif
+#ifndef YAMD_S1_RFIELD
+#define YAMD_S1_RFIELD 1
+#endif
+
+// w >> f[0..4], or with kHi w >> f[16..20]
+template <bool kHi>
+__device__ __forceinline__ uint32_t shr_field(uint32_t w, uint32_t f) {
+  if constexpr (!kHi) return w >> (f & 31u);
+  uint32_t r;
+  asm("v_lshrrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD"
+      : "=v"(r) : "v"(f), "v"(w));
+  return r;
+}
+
+// LDS byte address of pair j's filter block x[10..23] (8 bytes each).
+__device__ __forceinline__ uint32_t pair_block_addr(const uint32_t (&S)[6], uint32_t j) {
+  if (YAMD_S1_ALIGNBIT && (j & 1) == 0)   // bits 26..39 of S[m+1]:S[m] onto address bits 3..16
+    return __builtin_amdgcn_alignbit(S[j / 2 + 1], S[j / 2], 23) & (kFilterBytes - 8);
+  return (pair_window(S, j) >> 7) & (kFilterBytes - 8);
+}
+
+// The left window of pair j (position 2j) against its block w: u = the low
+// word shifted by x[0..4], v = the high word by x[5..9] (filter_probe_left;
+// bit 0 of u & v is the result).  kX: the caller forms x of even pairs anyway
+// (the hashed block index multiplies the whole window).
+template <bool kX>
+__device__ __forceinline__ void left_shifts(const uint32_t (&S)[6], uint32_t j, uint32_t w_lo,
+                                            uint32_t w_hi, uint32_t& u, uint32_t& v) {
+  const uint32_t m = (j + 1) >> 1;   // odd j = 2m - 1: x = S[m]; even j = 2m: x = (S[m+1]:S[m]) >> 16
+  if (j & 1) {
+    u = shr_field<false>(w_lo, S[m]);
+    v = shr_field<false>(w_hi, S[m] >> 5);
+    return;
+  }
+  const bool have_x = kX || !YAMD_S1_ALIGNBIT;
+  u = have_x ? shr_field<false>(w_lo, pair_window(S, j)) : shr_field<true>(w_lo, S[m]);
+  v = YAMD_S1_LFIELD ? shr_field<true>(w_hi, S[m] >> 5)
+      : have_x       ? shr_field<false>(w_hi, pair_window(S, j) >> 5)
+                     : shr_field<false>(w_hi, S[m] >> 21);
+}
+
+// The right windows of pairs 2m and 2m + 1 from one v_perm of the context
+// dwords S[m], S[m+1]: y2 = d(2m) | b(2m) << 8 | d(2m+1) << 16 | b(2m+1) << 24
+// (0.9 % faster than one v_perm per pair, profiles/r02_pair_perm_ab.json)
+__device__ __forceinline__ uint32_t right_windows(const uint32_t (&S)[6], uint32_t m) {
+  return __builtin_amdgcn_perm(S[m + 1], S[m], 0x05070305u);
+}
+
+// The right window of pair j (position 2j + 1), y = d | b << 8 in the low (even
+// j) or high (odd j) half of y2 = right_windows(S, j / 2): u, v as above with
+// the fields y[0..4], y[5..9] (filter_probe_right).
+__device__ __forceinline__ void right_shifts(uint32_t y2, uint32_t j, uint32_t w_lo, uint32_t w_hi,
+                                             uint32_t& u, uint32_t& v) {
+  if (j & 1) {
+    u = shr_field<true>(w_lo, y2);
+    v = YAMD_S1_RFIELD ? shr_field<true>(w_hi, y2 >> 5) : shr_field<false>(w_hi, y2 >> 21);
+  } else {
+    u = shr_field<false>(w_lo, y2);
+    v = shr_field<false>(w_hi, y2 >> 5);
+  }
+}
+
 // Per-wave LDS ring of filter hits awaiting the exact check.  One entry (24
 // bytes) per (tile, lane) with at least one hit: the lane's 16 bytes, the 4
 // bytes before them, and the lane byte offset in the segment / 16.
@@ -488,9 +571,11 @@ __device__ __forceinline__ uint32_t even_mask(const uint32_t (&S)[6]) {
   uint32_t m = 0;
 #pragma unroll
   for (int j = 0; j < kBytesPerLane / 2; ++j) {
-    const uint32_t x = pair_window(S, (uint32_t)j);
-    const u32x2 w = lds_load<u32x2>(even_addr<kHash>(x));
-    m |= ((w.x >> (x & 31u)) & (w.y >> ((x >> 5) & 31u)) & 1u) << (2 * j);
+    const u32x2 w = lds_load<u32x2>(kHash ? even_addr<true>(pair_window(S, (uint32_t)j))
+                                          : pair_block_addr(S, (uint32_t)j));
+    uint32_t u, v;
+    left_shifts<kHash>(S, (uint32_t)j, w.x, w.y, u, v);
+    m |= (u & v & 1u) << (2 * j);
   }
   return m | (m << 1);
 }
@@ -1252,8 +1337,10 @@ template <int MODE, bool kAny>
 __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane) {
   // Phase A: the lane's 8 position pairs and their 8 filter-block reads.
   // Pair j covers lane bytes k = 2j and k + 1; xs[j] = bytes k-2 .. k+1
-  // (stream offset k + 2: even, so an aligned dword or one alignbyte).
+  // (stream offset k + 2: even, so an aligned dword or one alignbyte; formed
+  // only where something reads it -- pair_block_addr, left_shifts).
   constexpr int kPairs = kBytesPerLane / 2;
+  constexpr bool kX = MODE == kModeEvenHash;
   uint32_t xs[kPairs];
   uint2 ws[kPairs];
 #pragma unroll
@@ -1262,7 +1349,7 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
     if constexpr (MODE != 3) {
       const uint32_t x = xs[j];
       uint32_t addr = MODE == kModeEvenHash ? even_addr<true>(x)      // hashed block
-                                            : (x >> 7) & (kFilterBytes - 8);   // block x[10..23], 8 B each
+                                            : pair_block_addr(S, j);  // block x[10..23], 8 B each
       if constexpr (MODE == 4) addr = ((lane & 31u) * 8u + (uint32_t)j * 256u) & (kFilterBytes - 8);
       if constexpr (MODE == 5) {
         ws[j] = make_uint2(addr ^ x, addr + x);
@@ -1279,7 +1366,8 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
   // filter_probe_left / _right): left (position k) bit x[0..4] of the lo word
   // and x[5..9] of the hi word; right (position k + 1) the same fields of
   // y = d | b << 8 (one v_perm).  The shifter reads only the low 5 bits of the
-  // amount.  The AND of the two shifted words is written by one SDWA v_and
+  // amount (left_shifts, right_shifts: 12 of the 32 test shifts take theirs
+  // through an SDWA select).  The AND of the two shifted words is written by one SDWA v_and
   // straight into byte n of accumulator r (position 4n + r), so bit 0 of that
   // byte is the position's result and no separate accumulate instruction is
   // needed; bits 1..7 of each byte are don't-care and masked off below.
@@ -1289,8 +1377,8 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
     uint32_t a[2];
 #pragma unroll
     for (int j = 0; j < kPairs; ++j) {
-      const uint32_t x = xs[j];
-      const uint32_t ul = ws[j].x >> (x & 31u), vl = ws[j].y >> ((x >> 5) & 31u);
+      uint32_t ul, vl;
+      left_shifts<kX>(S, j, ws[j].x, ws[j].y, ul, vl);
       uint32_t& aq = a[j >> 2];
       if ((j & 3) == 0) aq = ul & vl;
       else asm("v_bitop3_b32 %0, %1, %2, %0 bitop3:0xea" : "+v"(aq) : "v"(ul), "v"(vl));
@@ -1304,18 +1392,14 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
     // bit 0; the drain recomputes the per-position results of the few lanes
     // that do.  Two accumulators (pairs 0-3, 4-7) for some ILP.
     uint32_t a[2];
-    // the right windows of pairs 2m and 2m+1 from ONE v_perm of the context
-    // dwords S[m], S[m+1]: y2 = d(2m) | b(2m) << 8 | d(2m+1) << 16 | b(2m+1) << 24
-    // (0.9 % faster than one v_perm per pair, profiles/r02_pair_perm_ab.json)
     uint32_t y2[kPairs / 2];
 #pragma unroll
-    for (int m = 0; m < kPairs / 2; ++m) y2[m] = __builtin_amdgcn_perm(S[m + 1], S[m], 0x05070305u);
+    for (int m = 0; m < kPairs / 2; ++m) y2[m] = right_windows(S, m);
 #pragma unroll
     for (int j = 0; j < kPairs; ++j) {
-      const uint32_t x = xs[j];
-      const uint32_t ul = ws[j].x >> (x & 31u), vl = ws[j].y >> ((x >> 5) & 31u);
-      const uint32_t y = (j & 1) ? y2[j >> 1] >> 16 : y2[j >> 1];   // d | b << 8 (low 10 bits)
-      const uint32_t ur = ws[j].x >> (y & 31u), vr = ws[j].y >> ((y >> 5) & 31u);
+      uint32_t ul, vl, ur, vr;
+      left_shifts<kX>(S, j, ws[j].x, ws[j].y, ul, vl);
+      right_shifts(y2[j >> 1], j, ws[j].x, ws[j].y, ur, vr);
       uint32_t& aq = a[j >> 2];
       if ((j & 3) == 0) aq = ul & vl;
       // acc |= u & v in one v_bitop3 (S0 = u, S1 = v, S2 = acc: 0xF0 & 0xCC | 0xAA)
@@ -1344,11 +1428,9 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
     default: asm("v_and_b32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" \
                  : "+v"(acc[(K) & 3]) : "v"(U), "v"(V)); break;                                  \
   }
-  // (the right windows' d | b << 8 of two pairs from one v_perm, as in the
-  // kAny form above)
   uint32_t y2[kPairs / 2];
 #pragma unroll
-  for (int m = 0; m < kPairs / 2; ++m) y2[m] = __builtin_amdgcn_perm(S[m + 1], S[m], 0x05070305u);
+  for (int m = 0; m < kPairs / 2; ++m) y2[m] = right_windows(S, m);
 #pragma unroll
   for (int j = 0; j < kPairs; ++j) {
     const int k = 2 * j;
@@ -1358,11 +1440,10 @@ __device__ __forceinline__ uint32_t stage1(const uint32_t (&S)[6], uint32_t lane
     } else if constexpr (MODE == 6) {
       acc[k & 3] ^= ws[j].x ^ ws[j].y;
     } else {
-      const uint32_t x = xs[j];
-      const uint32_t ul = ws[j].x >> (x & 31u), vl = ws[j].y >> ((x >> 5) & 31u);
+      uint32_t ul, vl, ur, vr;
+      left_shifts<kX>(S, j, ws[j].x, ws[j].y, ul, vl);
       YAMD_SDWA_AND(k, ul, vl);
-      const uint32_t y = (j & 1) ? y2[j >> 1] >> 16 : y2[j >> 1];   // d | b << 8 (low 10 bits)
-      const uint32_t ur = ws[j].x >> (y & 31u), vr = ws[j].y >> ((y >> 5) & 31u);
+      right_shifts(y2[j >> 1], j, ws[j].x, ws[j].y, ur, vr);
       YAMD_SDWA_AND(k + 1, ur, vr);
     }
   }

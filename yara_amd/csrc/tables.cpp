@@ -357,8 +357,8 @@ int flatten_tables(const uint32_t* T, const uint32_t* M, uint32_t n_slots,
       // Other shapes: a per-tile issue model in VALU-equivalents per 1 KiB tile
       // (~7 us of a 4 GiB scan each; fitted to the kernel times of rx, short,
       // hex, fuzz1, fuzz4, bytekeys and C under both filters,
-      // profiles/r03_even_shapes_ab.json): stage 1 (pair 91, even 55, hashed
-      // even 63) + 12 per 1-byte key tested + the ring append in tiles with an
+      // profiles/r03_even_shapes_ab.json): stage 1 (pair 83, even 51, hashed
+      // even 63: the kernels' ISA counts) + 12 per 1-byte key tested + the ring append in tiles with an
       // entry (12) + per entry of certain 1-byte-key hits 6 and per entry of
       // filter passes 5 (first level) or 23 (2-byte keys: every hit position
       // goes to the bucket probes), never below the kernel's floor (pair 100,
@@ -385,8 +385,8 @@ int flatten_tables(const uint32_t* T, const uint32_t* M, uint32_t n_slots,
       };
       // (+12 per 2-byte key tested as half-words: 3 per dword, like a 1-byte key)
       const double s_pair = pair_test ? 12.0 * out.keys_by_len[2] : 0.0;
-      const double c_pair = cost(91.0, 100.0, pass_sum(out.filter) / 16777216.0, kBytesPerLane);
-      const double c_even[2] = {cost(55.0 + s_pair, 89.0, pass_plain_new / 16777216.0, kBytesPerLane / 2),
+      const double c_pair = cost(83.0, 100.0, pass_sum(out.filter) / 16777216.0, kBytesPerLane);
+      const double c_even[2] = {cost(51.0 + s_pair, 89.0, pass_plain_new / 16777216.0, kBytesPerLane / 2),
                                 cost(63.0 + s_pair, 89.0, pass[1] / 16777216.0, kBytesPerLane / 2)};
       const int h = c_even[1] < c_even[0] ? 1 : 0;
       if (c_even[h] < 0.97 * c_pair) pick = h;
