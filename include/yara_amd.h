@@ -513,8 +513,8 @@ typedef struct
  *
  * Both are DEVICE pointers owned by the scanner, valid until its next verify
  * or match call.  Synchronous.  YR_AMD_INVALID_ARGUMENT: everything
- * yr_amd_verify_device refuses, no completed scan, a batch scan (its key would
- * need the buffer index), tables with yr_amd_tables_set_profiling enabled
+ * yr_amd_verify_device refuses, no completed scan, a batch scan (that is
+ * yr_amd_match_batch_device's), tables with yr_amd_tables_set_profiling enabled
  * (count-only records are no calls), more than YR_AMD_MATCH_MAX_RECORDS
  * records, and a block of more than YR_AMD_MATCH_MAX_BLOCK bytes: the stage
  * keys a match by its offset in 32 bits, and offsets are positions of the
@@ -699,6 +699,60 @@ int yr_amd_scan_batch_gather_device(
     const uint8_t* const* d_buffers,
     const uint64_t* sizes,
     uint64_t n);
+
+/*
+ * ---- Final matches of a batch ----
+ *
+ * yr_amd_match_device for the last completed batch scan (yr_amd_scan_batch_device
+ * or yr_amd_scan_batch_gather_device, then yr_amd_scan_batch_result): runs
+ * yr_amd_verify_batch_device itself (same preconditions, same bases) and then,
+ * on the scanner's stream, splits its records, keyed by (buffer, string,
+ * offset).  Buffer k gets exactly what yr_amd_scan_block_matches(data_k,
+ * size_k, bases[k]) returns for that buffer alone:
+ *
+ * matches[match_off[k] .. match_off[k + 1]): one entry per distinct (string,
+ * offset) among buffer k's records of final strings, ascending by (string,
+ * offset), offsets local to the buffer; the first record in record order
+ * supplies length, xor_key and pool_index (the rules of yr_amd_match_device).
+ * Equal (string, offset) pairs of different buffers are different matches.
+ * rest[rest_off[k] .. rest_off[k + 1]): buffer k's other records in their
+ * original order, every field unchanged (candidate indexes the buffer's own
+ * stream).  YR_MAX_STRING_MATCHES is not applied.
+ *
+ * *d_matches / *d_rest are DEVICE pointers, *match_off / *rest_off HOST
+ * pointers to n + 1 offsets (one element, 0, for n == 0), all owned by the
+ * scanner and valid until its next verify or match call.  Any of the four may
+ * be NULL.  Synchronous.  Without records no kernel is launched and every
+ * offset is 0.  YR_AMD_INVALID_ARGUMENT: everything yr_amd_verify_batch_device
+ * refuses (no strings, root-accepting rules, a pending scan, a batch whose
+ * result was not collected, a single-block scan), tables with
+ * yr_amd_tables_set_profiling enabled, and more than YR_AMD_MATCH_MAX_RECORDS
+ * records.  No size limit beyond the batch's own: an arena is below 4 GiB, so
+ * every local offset fits the key's 32 bits.
+ */
+int yr_amd_match_batch_device(
+    yr_amd_scanner* scanner,
+    const uint64_t* bases,
+    const yr_amd_match_rec** d_matches,
+    const uint64_t** match_off,
+    const yr_amd_verify_rec** d_rest,
+    const uint64_t** rest_off);
+
+/*
+ * Host convenience, the path of yr_amd_scan_batch_verified (pack, one H2D
+ * copy, batch scan, result), then the match stage and the D2H copies.  All four
+ * outputs are host arrays owned by the scanner (valid until its next call).
+ */
+int yr_amd_scan_batch_matches(
+    yr_amd_scanner* scanner,
+    const uint8_t* const* data,
+    const size_t* sizes,
+    const uint64_t* bases,
+    size_t n,
+    const yr_amd_match_rec** matches,
+    const uint64_t** match_off,
+    const yr_amd_verify_rec** rest,
+    const uint64_t** rest_off);
 
 /*
  * ---- Block pipeline ----

@@ -1,6 +1,6 @@
 """Which literal strings of a compiled rules file match where in a file.
 
-    python tools/string_matches.py RULES.yarc FILE
+    python tools/string_matches.py RULES.yarc FILE [FILE ...]
 
 Prints one "string offset length xor" line per match of a final string
 (include/yara_amd.h: literal, not a chain part, not base64) -- absolute file
@@ -18,6 +18,14 @@ FULL_WORD string next to a block's edge is judged by the file's bytes, not by
 the edge.  That equals the one-block result for strings shorter than OVERLAP /
 2 bytes; the count of calls left is the blocks' sum, calls in the overlaps
 counted twice.
+
+Several files: the output lines are "path string offset length xor", in the
+order of the arguments.  Files of at most BLOCK bytes go through batches --
+one scan, one pre-verification and one match stage for all files of an arena
+(yr_amd_scan_batch_matches) -- the arenas packed below ARENA bytes, the files
+split across several arenas when needed; every such file is one buffer, so
+its lines are those of a stock scan of the file.  A larger file takes the
+block path above.
 """
 import gzip
 import os
@@ -29,18 +37,12 @@ sys.path.insert(0, REPO)
 BLOCK = 1 << 30      # blocks of 1 GiB ...
 OVERLAP = 1 << 16    # ... overlapping: a match near a block's edge is taken from the block
                      # that holds OVERLAP / 2 bytes on either side of its start
+ARENA = (1 << 32) - (1 << 20)   # a batch's packed arena stays below 4 GiB
 
 
-def main():
-    if len(sys.argv) != 3:
-        sys.exit(__doc__)
-    import numpy as np
+def block_path(sc, data):
+    """(matches with absolute offsets, calls left) of one file, block-wise."""
     import yara_amd
-    opener = gzip.open if sys.argv[1].endswith(".gz") else open
-    with opener(sys.argv[1], "rb") as f:
-        tables = yara_amd.Tables.from_yarc(f.read(), device=0)
-    data = np.fromfile(sys.argv[2], dtype=np.uint8)
-    sc = yara_amd.Scanner(tables)
     blocks, left, base = [], 0, 0
     while True:
         last = base + BLOCK >= data.size
@@ -53,8 +55,60 @@ def main():
         if last:
             break
         base += BLOCK - OVERLAP
-    for r in yara_amd.merge_matches(blocks):
-        print(r["string"], r["offset"], r["length"], r["xor_key"])
+    return yara_amd.merge_matches(blocks), left
+
+
+def arenas(sizes):
+    """The files of at most BLOCK bytes, in order, grouped into arenas whose
+    packed size (16-byte aligned starts) stays below ARENA."""
+    groups, used = [], 0
+    for k, n in enumerate(sizes):
+        if n > BLOCK:
+            continue
+        need = (n + 15) // 16 * 16
+        if not groups or used + need > ARENA:
+            groups.append([])
+            used = 0
+        groups[-1].append(k)
+        used += need
+    return groups
+
+
+def main():
+    if len(sys.argv) < 3:
+        sys.exit(__doc__)
+    import numpy as np
+    import yara_amd
+    opener = gzip.open if sys.argv[1].endswith(".gz") else open
+    with opener(sys.argv[1], "rb") as f:
+        tables = yara_amd.Tables.from_yarc(f.read(), device=0)
+    sc = yara_amd.Scanner(tables)
+    paths = sys.argv[2:]
+    if len(paths) == 1:
+        matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))
+        for r in matches:
+            print(r["string"], r["offset"], r["length"], r["xor_key"])
+        print("%d verify calls left for a host verifier" % left, file=sys.stderr)
+        return
+    sizes = [os.path.getsize(p) for p in paths]
+    per, left = [None] * len(paths), 0
+    for group in arenas(sizes):
+        try:
+            m, mo, rest, _ = sc.batch_string_matches(
+                [np.fromfile(paths[k], dtype=np.uint8) for k in group])
+        except yara_amd.YaraAmdError as e:
+            if e.code != yara_amd.INVALID_ARGUMENT:
+                raise
+            break   # rules with a root match list take no batches: file by file below
+        for j, k in enumerate(group):
+            per[k] = m[int(mo[j]):int(mo[j + 1])]
+        left += len(rest)
+    for k, p in enumerate(paths):
+        if per[k] is None:   # larger than BLOCK
+            per[k], n = block_path(sc, np.fromfile(p, dtype=np.uint8))
+            left += n
+        for r in per[k]:
+            print(p, r["string"], r["offset"], r["length"], r["xor_key"])
     print("%d verify calls left for a host verifier" % left, file=sys.stderr)
 
 

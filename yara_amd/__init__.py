@@ -498,6 +498,71 @@ class Scanner:
         self.batch_result()
         return self.verify_batch_device(bases)
 
+    # -- final matches of a batch ------------------------------------------------
+    def match_batch_device(self, bases=None):
+        """(matches, match_off, rest, rest_off) of the last completed batch scan
+        (yr_amd_match_batch_device), copied to the host: buffer k's
+        ``matches[match_off[k]:match_off[k + 1]]`` and
+        ``rest[rest_off[k]:rest_off[k + 1]]`` are what ``string_matches`` gives
+        for that buffer alone (offsets local to the buffer)."""
+        from ._hip import memcpy
+        b = None if bases is None else _arr(bases, np.uint64).reshape(-1)
+        if b is not None and b.size != self._batch_n:
+            raise ValueError("one base per buffer")
+        pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
+        mo, ro = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+        _lib.check("yr_amd_match_batch_device", _lib.lib().yr_amd_match_batch_device(
+            self._h, b.ctypes.data_as(_lib._u64p) if b is not None and b.size else None,
+            ctypes.byref(pm), ctypes.byref(mo), ctypes.byref(pr), ctypes.byref(ro)))
+        match_off = np.ctypeslib.as_array(mo, shape=(self._batch_n + 1,)).copy()
+        rest_off = np.ctypeslib.as_array(ro, shape=(self._batch_n + 1,)).copy()
+        matches = np.zeros(int(match_off[-1]), dtype=_lib.MATCH_REC_DTYPE)
+        rest = np.zeros(int(rest_off[-1]), dtype=_lib.VERIFY_REC_DTYPE)
+        if matches.size:
+            memcpy(matches.ctypes.data, pm.value, matches.size * 24, 2)
+        if rest.size:
+            memcpy(rest.ctypes.data, pr.value, rest.size * 16, 2)
+        return matches, match_off, rest, rest_off
+
+    def batch_string_matches(self, buffers, bases=None):
+        """(matches, match_off, rest, rest_off) of a list of host buffers
+        (yr_amd_scan_batch_matches): buffer k's slices equal
+        ``string_matches(buffers[k], bases[k])``.  One scan, one
+        pre-verification and one match stage for all of them."""
+        bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
+        n = len(bufs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+        sizes = (ctypes.c_size_t * max(n, 1))(*[b.size for b in bufs])
+        b = None if bases is None else _arr(bases, np.uint64).reshape(-1)
+        if b is not None and b.size != n:
+            raise ValueError("one base per buffer")
+        pm = ctypes.POINTER(_lib.MatchRec)()
+        pr = ctypes.POINTER(_lib.VerifyRec)()
+        mo, ro = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+        _lib.check("yr_amd_scan_batch_matches", _lib.lib().yr_amd_scan_batch_matches(
+            self._h, ptrs, sizes, b.ctypes.data_as(_lib._u64p) if b is not None and b.size else None,
+            n, ctypes.byref(pm), ctypes.byref(mo), ctypes.byref(pr), ctypes.byref(ro)))
+        self._batch_n = n
+        match_off = np.ctypeslib.as_array(mo, shape=(n + 1,)).copy()
+        rest_off = np.ctypeslib.as_array(ro, shape=(n + 1,)).copy()
+        matches = np.zeros(int(match_off[-1]), dtype=_lib.MATCH_REC_DTYPE)
+        rest = np.zeros(int(rest_off[-1]), dtype=_lib.VERIFY_REC_DTYPE)
+        if matches.size:
+            ctypes.memmove(matches.ctypes.data, pm, matches.size * 24)
+        if rest.size:
+            ctypes.memmove(rest.ctypes.data, pr, rest.size * 16)
+        return matches, match_off, rest, rest_off
+
+    def batch_string_matches_device(self, buffers, bases=None):
+        """batch_string_matches for buffers in device memory (see
+        batch_candidates_device), through the gather call."""
+        ptrs, sizes = _device_buffers(buffers)
+        if bases is not None and _arr(bases, np.uint64).size != ptrs.size:
+            raise ValueError("one base per buffer")
+        self.scan_batch_gather_device(ptrs, sizes)
+        self.batch_result()
+        return self.match_batch_device(bases)
+
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):
         if byte_end is None:

@@ -156,6 +156,14 @@ PROTOTYPES = {
                                           ctypes.POINTER(_u64p)]),
     "yr_amd_batch_gather": (_int, [_vp, _vp, ctypes.c_uint64, _u64p, _u64p, _u64p, ctypes.c_uint64]),
     "yr_amd_scan_batch_gather_device": (_int, [_vp, _u64p, _u64p, ctypes.c_uint64]),
+    "yr_amd_match_batch_device": (_int, [_vp, _u64p, ctypes.POINTER(_vp), ctypes.POINTER(_u64p),
+                                         ctypes.POINTER(_vp), ctypes.POINTER(_u64p)]),
+    "yr_amd_scan_batch_matches": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_size_t),
+                                         _u64p, ctypes.c_size_t,
+                                         ctypes.POINTER(ctypes.POINTER(MatchRec)),
+                                         ctypes.POINTER(_u64p),
+                                         ctypes.POINTER(ctypes.POINTER(VerifyRec)),
+                                         ctypes.POINTER(_u64p)]),
     "yr_amd_tables_device": (_int, [_vp]),
     "yr_amd_tables_set_profiling": (_int, [_vp, _int]),
 }

@@ -75,4 +75,39 @@ hipError_t match_sort(uint64_t* const keys[2], uint32_t* const index[2], uint64_
 // the first entry of every run of equal keys as a MatchRec.
 hipError_t launch_match_unique(const MatchParams& p, int pass, hipStream_t s);
 
+// ---- The same stage for a batch (yr_amd_match_batch_device) ----
+// The key gets a third, most significant field, the record's buffer, kept in
+// an array of its own (any n fits: no batch is refused for key width).  The
+// records of a batch lie in buffer order, rec_off[] their CSR; the sort by
+// (buffer, string, offset) keeps every buffer's entries in the very slots
+// [rec_off[k], rec_off[k + 1]) -- which is what the CSR offsets of the
+// matches are counted from.
+// A struct of its own: MatchParams is a kernel argument of the single-block
+// kernels, which stay what they are.
+struct BatchMatchParams {
+  MatchParams m;                // data = the arena; size, win_lo, win_hi unused
+  const uint64_t* starts;       // [nbuf] the buffers in the arena
+  const uint64_t* sizes;        // [nbuf]
+  const uint64_t* rec_off;      // [nbuf + 1] CSR of m.recs (yr_amd_verify_batch_device)
+  uint32_t nbuf;
+  uint32_t* buf;                // [m.n] by record: its buffer
+  uint64_t* match_off;          // [nbuf + 1] CSR of m.out
+  uint64_t* rest_off;           // [nbuf + 1] CSR of m.rest
+};
+
+// Classify: as launch_match_classify, each record measured in its own buffer, + buf.
+hipError_t launch_batch_match_classify(const BatchMatchParams& p, hipStream_t s);
+// rest_off from the scanned rest counts (before anything reuses block_off), and
+// match_off from the scanned unique counts (after launch_batch_match_unique 0).
+hipError_t launch_batch_match_offsets(const BatchMatchParams& p, int matches, hipStream_t s);
+// match_sort, then the passes over the bits of nbuf - 1 (none for nbuf == 1),
+// digits read from buf through the sorted index.
+hipError_t batch_match_sort(uint64_t* const keys[2], uint32_t* const index[2], uint64_t n,
+                            int lo_bits, int hi_bits, const uint32_t* buf, uint32_t nbuf,
+                            uint64_t* hist, uint64_t* chunk, uint64_t* total, hipStream_t s,
+                            int* result);
+// As launch_match_unique; an entry is kept iff it is a match and its (buffer,
+// key) differs from its predecessor's.
+hipError_t launch_batch_match_unique(const BatchMatchParams& p, int pass, hipStream_t s);
+
 }  // namespace yamd

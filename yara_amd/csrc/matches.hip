@@ -259,6 +259,154 @@ __global__ __launch_bounds__(64) void sort_scatter_kernel(SortPass p) {
   }
 }
 
+// The twins of the two kernels above for the batch's buffer passes: the digit
+// is of the buffer of the record that the item's value names.  (Twins, not a
+// template over both: the single-block kernels stay instruction for
+// instruction what they were.)
+struct SortPassBuf {
+  SortPass s;
+  const uint32_t* buf;      // [n] by record; digit = (buf[value] >> shift) & mask
+};
+
+__global__ __launch_bounds__(64) void sort_hist_buf_kernel(SortPassBuf q) {
+  __shared__ uint32_t cnt[256];
+  const SortPass& p = q.s;
+  const uint32_t lane = threadIdx.x;
+  const uint64_t t = blockIdx.x;
+  for (uint32_t d = lane; d < 256; d += 64) cnt[d] = 0;
+  __syncthreads();
+  const uint64_t lo = t * kSortTile, hi = min(lo + (uint64_t)kSortTile, p.n);
+  for (uint64_t i = lo + lane; i < hi; i += 64)
+    atomicAdd(&cnt[(q.buf[p.vin[i]] >> p.shift) & p.mask], 1u);
+  __syncthreads();
+  for (uint32_t d = lane; d <= p.mask; d += 64) p.hist[(uint64_t)d * p.tiles + t] = cnt[d];
+}
+
+__global__ __launch_bounds__(64) void sort_scatter_buf_kernel(SortPassBuf q) {
+  __shared__ uint32_t cnt[256];   // per digit: the next output slot of this tile
+  const SortPass& p = q.s;
+  const uint32_t lane = threadIdx.x;
+  const uint64_t t = blockIdx.x;
+  for (uint32_t d = lane; d <= p.mask; d += 64) {
+    const uint64_t e = (uint64_t)d * p.tiles + t;
+    cnt[d] = (uint32_t)(p.chunk[e / kChunkGroups] + p.hist[e]);   // (n < 2^31)
+  }
+  __syncthreads();
+  const uint64_t lo = t * kSortTile, hi = min(lo + (uint64_t)kSortTile, p.n);
+  for (uint64_t base = lo; base < hi; base += 64) {   // (uniform: barriers inside)
+    const uint64_t i = base + lane;
+    const bool valid = i < hi;
+    const uint64_t key = valid ? p.kin[i] : 0ull;
+    const uint32_t val = valid ? p.vin[i] : 0u;
+    const uint32_t d = valid ? (q.buf[val] >> p.shift) & p.mask : 0u;
+    uint64_t peers = __ballot(valid);   // the valid lanes with this lane's digit
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t m = __ballot(valid && bit);
+      peers &= bit ? m : ~m;
+    }
+    const uint32_t rank = lanes_below(peers);
+    const uint32_t pos = valid ? cnt[d] + rank : 0u;
+    __syncthreads();
+    if (valid && rank == 0) cnt[d] += (uint32_t)__popcll(peers);
+    __syncthreads();
+    if (valid) {
+      p.kout[pos] = key;
+      p.vout[pos] = val;
+    }
+  }
+}
+
+// ---- The stage for a batch (matches.h BatchMatchParams) ----
+// One lane per record: its buffer b is the one with rec_off[b] <= r <
+// rec_off[b + 1] (empty buffers have no such r); measure() then sees the
+// buffer as the whole block, as the batch pre-verification did -- no byte
+// outside [starts[b], starts[b] + sizes[b]) is read, none in a gap.
+__global__ __launch_bounds__(256) void batch_match_classify_kernel(BatchMatchParams p) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool rest = false;
+  if (r < p.m.n) {
+    uint32_t lo = 0, hi = p.nbuf;   // rec_off[lo] <= r < rec_off[hi]  (rec_off[nbuf] == n)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (p.rec_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    MatchParams q = p.m;
+    q.data = p.m.data + p.starts[lo];
+    q.size = p.sizes[lo];
+    q.win_lo = 0;
+    q.win_hi = q.size;
+    const VerifyRec rec = p.m.recs[r];
+    const DevPoolRec e = p.m.pool[rec.pool_index];
+    MatchMeasure m;
+    const bool is_match = measure(q, e, rec.offset, m);
+    const uint32_t string = is_match ? p.m.pool_string[rec.pool_index] : p.m.n_strings;
+    p.m.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.m.index[r] = (uint32_t)r;
+    p.m.meas[r] = m;
+    p.buf[r] = lo;
+    rest = !is_match;
+  }
+  const uint64_t mask = __ballot(rest);
+  if ((threadIdx.x & 63u) == 0 && r < p.m.n) p.m.block_off[r / kGroup] = (uint64_t)__popcll(mask);
+}
+
+// Entry i of the sorted arrays opens a run of one (buffer, string, offset).
+__device__ __forceinline__ bool batch_keep(const BatchMatchParams& p, uint64_t i, uint64_t key) {
+  if ((uint32_t)(key >> 32) >= p.m.n_strings) return false;
+  return i == 0 || p.m.sorted_keys[i - 1] != key ||
+         p.buf[p.m.sorted_index[i - 1]] != p.buf[p.m.sorted_index[i]];
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void batch_match_unique_kernel(BatchMatchParams p) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  uint64_t key = 0;
+  if (i < p.m.n) {
+    key = p.m.sorted_keys[i];
+    keep = batch_keep(p, i, key);
+  }
+  const uint64_t mask = __ballot(keep);
+  if (PASS == 0) {
+    if ((threadIdx.x & 63u) == 0 && i < p.m.n) p.m.block_off[i / kGroup] = (uint64_t)__popcll(mask);
+    return;
+  }
+  if (!keep) return;
+  const uint32_t r = p.m.sorted_index[i];   // the buffer's first call of this (string, offset)
+  const MatchMeasure m = p.m.meas[r];
+  MatchRec o;
+  o.offset = key & 0xFFFFFFFFull;
+  o.string = (uint32_t)(key >> 32);
+  o.length = m.length;
+  o.xor_key = m.xor_key;
+  o.pool_index = p.m.recs[r].pool_index;
+  p.m.out[wave_offset(p.m, i / kGroup) + lanes_below(mask)] = o;
+}
+
+// The CSR offsets, one lane per k in [0, nbuf].  Buffer k's records hold the
+// slots [rec_off[k], rec_off[k + 1]) in record order and -- the buffer being
+// the sort's most significant field -- in sorted order too, so the outputs
+// before buffer k are those of the slots below c0 = rec_off[k]: the scanned
+// count of c0's wave plus the flags of the wave's slots below c0 (as
+// verify.hip's batch_rec_offsets_kernel counts records).  MATCHES 0: the rest
+// records (keys in record order); 1: the kept entries (sorted arrays).
+template <int MATCHES>
+__global__ __launch_bounds__(256) void batch_match_offsets_kernel(BatchMatchParams p) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > p.nbuf) return;
+  const uint64_t c0 = p.rec_off[k], g = c0 / kGroup;
+  uint64_t o = wave_offset(p.m, g);   // (g == groups: the entry past the last wave, the total)
+  for (uint64_t c = g * kGroup; c < c0; ++c) {
+    if (MATCHES)
+      o += batch_keep(p, c, p.m.sorted_keys[c]) ? 1u : 0u;
+    else
+      o += (uint32_t)(p.m.keys[c] >> 32) == p.m.n_strings ? 1u : 0u;
+  }
+  (MATCHES ? p.match_off : p.rest_off)[k] = o;
+}
+
 }  // namespace
 
 hipError_t launch_match_classify(const MatchParams& p, hipStream_t s) {
@@ -314,6 +462,66 @@ hipError_t launch_match_unique(const MatchParams& p, int pass, hipStream_t s) {
     hipLaunchKernelGGL(match_unique_kernel<0>, match_grid(p.n), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(match_unique_kernel<1>, match_grid(p.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_match_classify(const BatchMatchParams& p, hipStream_t s) {
+  if (p.m.n == 0 || p.m.n > kMatchMaxRecords || p.nbuf == 0)
+    return p.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_match_classify_kernel, match_grid(p.m.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_match_offsets(const BatchMatchParams& p, int matches, hipStream_t s) {
+  if (p.m.n == 0 || p.m.n > kMatchMaxRecords) return p.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  const dim3 grid = match_grid((uint64_t)p.nbuf + 1);
+  if (matches)
+    hipLaunchKernelGGL(batch_match_offsets_kernel<1>, grid, dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(batch_match_offsets_kernel<0>, grid, dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t batch_match_sort(uint64_t* const keys[2], uint32_t* const index[2], uint64_t n,
+                            int lo_bits, int hi_bits, const uint32_t* buf, uint32_t nbuf,
+                            uint64_t* hist, uint64_t* chunk, uint64_t* total, hipStream_t s,
+                            int* result) {
+  hipError_t e = match_sort(keys, index, n, lo_bits, hi_bits, hist, chunk, total, s, result);
+  if (e != hipSuccess || n == 0 || nbuf < 2) return e;
+  int bits = 1;   // the bits of nbuf - 1
+  while (bits < 32 && ((nbuf - 1) >> bits) != 0) ++bits;
+  const KeptLists none{{0, 0, 0, 0}};
+  int src = *result;
+  for (int shift = 0; shift < bits; shift += 8) {
+    SortPassBuf p;
+    p.s.kin = keys[src];
+    p.s.kout = keys[src ^ 1];
+    p.s.vin = index[src];
+    p.s.vout = index[src ^ 1];
+    p.s.n = n;
+    p.s.tiles = match_sort_tiles(n);
+    p.s.shift = (uint32_t)shift;
+    p.s.mask = (1u << std::min(8, bits - shift)) - 1u;
+    p.s.hist = hist;
+    p.s.chunk = chunk;
+    p.buf = buf;
+    const uint64_t entries = (uint64_t)(p.s.mask + 1) * p.s.tiles;
+    hipLaunchKernelGGL(sort_hist_buf_kernel, dim3((uint32_t)p.s.tiles), dim3(64), 0, s, p);
+    e = launch_block_offsets(hist, chunk, entries * kGroup, total, nullptr, none, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sort_scatter_buf_kernel, dim3((uint32_t)p.s.tiles), dim3(64), 0, s, p);
+    src ^= 1;
+  }
+  *result = src;
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_match_unique(const BatchMatchParams& p, int pass, hipStream_t s) {
+  if (p.m.n == 0 || p.m.n > kMatchMaxRecords) return p.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (pass == 0)
+    hipLaunchKernelGGL(batch_match_unique_kernel<0>, match_grid(p.m.n), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(batch_match_unique_kernel<1>, match_grid(p.m.n), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

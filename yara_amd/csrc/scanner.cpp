@@ -230,6 +230,12 @@ struct yr_amd_scanner {
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
+  // the batch's match stage (yr_amd_match_batch_device; matches.h BatchMatchParams)
+  uint32_t* d_mbuf = nullptr;           // [cap] each record's buffer
+  size_t mbuf_cap = 0;
+  uint64_t* d_moff = nullptr;           // [2 * (n + 1)]: match_off, rest_off
+  size_t moff_cap = 0;
+  std::vector<uint64_t> h_match_off, h_mrest_off;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -525,7 +531,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_bunit, (void*)s->d_bunit_off, (void*)s->d_gather,
                   (void*)s->d_mkeys, (void*)s->d_mindex, (void*)s->d_mmeas, (void*)s->d_mrest,
                   (void*)s->d_mout, (void*)s->d_mblock, (void*)s->d_mchunk, (void*)s->d_mhist,
-                  (void*)s->d_mhchunk})
+                  (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1701,7 +1707,9 @@ int reallocate(T*& p, size_t need) {
   return grow(p, cap, need);
 }
 
-int ensure_match_workspace(yr_amd_scanner* s, uint64_t n) {
+// nbuf > 0: a batch of nbuf buffers, which needs the records' buffers and the
+// two CSR offset arrays too.
+int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (s->h_msum == nullptr) {
     if (hipHostMalloc((void**)&s->h_msum, 3 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
       s->h_msum = nullptr;
@@ -1731,6 +1739,8 @@ int ensure_match_workspace(yr_amd_scanner* s, uint64_t n) {
   const uint64_t hist = match_sort_hist(n);
   if (!r) r = grow_geo(s->d_mhist, s->mhist_cap, hist + 1);
   if (!r) r = grow_geo(s->d_mhchunk, s->mhchunk_cap, verify_chunks(hist * kGroup) + 1);
+  if (!r && nbuf > 0) r = grow_geo(s->d_mbuf, s->mbuf_cap, n);
+  if (!r && nbuf > 0) r = grow_geo(s->d_moff, s->moff_cap, 2 * ((size_t)nbuf + 1));
   return r;
 }
 }  // namespace
@@ -2057,9 +2067,11 @@ int yr_amd_verify_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   return YR_AMD_SUCCESS;
 }
 
-int yr_amd_scan_batch_verified(yr_amd_scanner* s, const uint8_t* const* data, const size_t* sizes,
-                               const uint64_t* bases, size_t n, const yr_amd_verify_rec** records,
-                               const uint64_t** rec_off) {
+extern "C++" {
+namespace {
+// Host buffers packed into pinned staging (gaps zeroed), one H2D copy, the
+// batch scan and its result: what the host conveniences share.
+int scan_batch_host(yr_amd_scanner* s, const uint8_t* const* data, const size_t* sizes, size_t n) {
   if (s == nullptr || n > YR_AMD_BATCH_MAX_BUFFERS || (n > 0 && (data == nullptr || sizes == nullptr)))
     return YR_AMD_INVALID_ARGUMENT;
   if (!s->tables->has_strings || s->tables->flat.root_accepting) return YR_AMD_INVALID_ARGUMENT;
@@ -2094,6 +2106,15 @@ int yr_amd_scan_batch_verified(yr_amd_scanner* s, const uint8_t* const* data, co
     return YR_AMD_COULD_NOT_MAP_FILE;
   r = yr_amd_scan_batch_device(s, s->d_block, arena, st.data(), sz.data(), n);
   if (!r) r = yr_amd_scan_batch_result(s, nullptr, nullptr, nullptr);
+  return r;
+}
+}  // namespace
+}  // extern "C++"
+
+int yr_amd_scan_batch_verified(yr_amd_scanner* s, const uint8_t* const* data, const size_t* sizes,
+                               const uint64_t* bases, size_t n, const yr_amd_verify_rec** records,
+                               const uint64_t** rec_off) {
+  int r = scan_batch_host(s, data, sizes, n);
   const yr_amd_verify_rec* d_rec = nullptr;
   const uint64_t* off = nullptr;
   if (!r) r = yr_amd_verify_batch_device(s, bases, &d_rec, &off);
@@ -2168,6 +2189,128 @@ int yr_amd_scan_batch_gather_device(yr_amd_scanner* s, const uint8_t* const* d_b
   r = yr_amd_batch_gather(s, s->d_block, arena, st.data(), d_buffers, sizes, n);
   if (r) return r;
   return yr_amd_scan_batch_device(s, s->d_block, arena, st.data(), sizes, n);
+}
+
+// ---- Final matches of a batch (matches.hip BatchMatchParams) ----
+
+int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
+                              const yr_amd_match_rec** d_matches, const uint64_t** match_off,
+                              const yr_amd_verify_rec** d_rest, const uint64_t** rest_off) {
+  if (s == nullptr) return YR_AMD_INVALID_ARGUMENT;
+  // (count-only records are no calls: they have no match meaning)
+  if (s->tables->profile) return YR_AMD_INVALID_ARGUMENT;
+  const yr_amd_tables* t = s->tables;
+  const yr_amd_verify_rec* d_rec = nullptr;
+  const uint64_t* rec_off = nullptr;
+  int r = yr_amd_verify_batch_device(s, bases, &d_rec, &rec_off);
+  if (r) return r;
+  const uint32_t nbuf = s->batch_n;
+  const uint64_t n = rec_off[nbuf];
+  if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
+  s->h_match_off.assign((size_t)nbuf + 1, 0);
+  s->h_mrest_off.assign((size_t)nbuf + 1, 0);
+  uint64_t nm = 0, nr = 0;
+  if (n > 0) {   // (no records: no kernel is launched)
+    r = ensure_match_workspace(s, n, nbuf);
+    if (r) return r;
+    BatchMatchParams p{};
+    p.m.data = s->last.data;
+    p.m.recs = reinterpret_cast<const VerifyRec*>(d_rec);
+    p.m.n = n;
+    p.m.pool = t->d_pool;
+    p.m.pool_string = t->d_pool_string;
+    p.m.n_strings = (uint32_t)t->h_str_flags.size();
+    p.m.str_bytes = t->d_str_bytes;
+    p.m.lowercase = t->d_lowercase;
+    p.m.keys = s->d_mkeys;
+    p.m.index = s->d_mindex;
+    p.m.meas = s->d_mmeas;
+    p.m.block_off = s->d_mblock;
+    p.m.chunk_off = s->d_mchunk;
+    p.m.rest = s->d_mrest;
+    p.m.out = s->d_mout;
+    p.starts = s->d_bstarts;
+    p.sizes = s->d_bstarts + nbuf;
+    p.rec_off = s->d_boff + (size_t)nbuf + 1;   // (built by yr_amd_verify_batch_device)
+    p.nbuf = nbuf;
+    p.buf = s->d_mbuf;
+    p.match_off = s->d_moff;
+    p.rest_off = s->d_moff + (size_t)nbuf + 1;
+    // the key's bits that vary: the local offsets' (below the largest buffer's
+    // size), and the string field's up to n_strings itself (the rest records')
+    uint64_t largest = 1;
+    for (uint64_t z : s->h_bsizes) largest = std::max(largest, z);
+    int lo_bits = 1, hi_bits = 1;
+    while (lo_bits < 32 && ((largest - 1) >> lo_bits) != 0) ++lo_bits;
+    while (hi_bits < 32 && (p.m.n_strings >> hi_bits) != 0) ++hi_bits;
+    uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+    uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+    const KeptLists none{{0, 0, 0, 0}};
+    // classify -> the rest's offsets -> the rest and its CSR; sort; distinct
+    // (buffer, key) -> their offsets -> the matches and their CSR; one wait
+    HIP_TRY(launch_batch_match_classify(p, s->stream));
+    HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum, nullptr, none,
+                                 s->stream));
+    HIP_TRY(launch_match_rest(p.m, s->stream));
+    HIP_TRY(launch_batch_match_offsets(p, 0, s->stream));
+    int sorted = 0;
+    HIP_TRY(batch_match_sort(keys, index, n, lo_bits, hi_bits, p.buf, nbuf, s->d_mhist,
+                             s->d_mhchunk, s->d_mhsum + 2, s->stream, &sorted));
+    p.m.sorted_keys = keys[sorted];
+    p.m.sorted_index = index[sorted];
+    HIP_TRY(launch_batch_match_unique(p, 0, s->stream));
+    HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum + 1, nullptr, none,
+                                 s->stream));
+    HIP_TRY(launch_batch_match_unique(p, 1, s->stream));
+    HIP_TRY(launch_batch_match_offsets(p, 1, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_match_off.data(), p.match_off, ((size_t)nbuf + 1) * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_mrest_off.data(), p.rest_off, ((size_t)nbuf + 1) * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    nr = s->h_msum[0];
+    nm = s->h_msum[1];
+    if (nr > n || nm > n - nr || s->h_match_off[nbuf] != nm || s->h_mrest_off[nbuf] != nr)
+      return YR_AMD_INTERNAL_FATAL_ERROR;
+  }
+  if (debug_level() >= 1)
+    fprintf(stderr,
+            "- %u buffers, %llu verify calls -> %llu matches, %llu calls left // "
+            "yr_amd_match_batch_device()\n",
+            nbuf, (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
+  if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
+  if (match_off) *match_off = s->h_match_off.data();
+  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(s->d_mrest);
+  if (rest_off) *rest_off = s->h_mrest_off.data();
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scan_batch_matches(yr_amd_scanner* s, const uint8_t* const* data, const size_t* sizes,
+                              const uint64_t* bases, size_t n, const yr_amd_match_rec** matches,
+                              const uint64_t** match_off, const yr_amd_verify_rec** rest,
+                              const uint64_t** rest_off) {
+  if (s == nullptr || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
+  int r = scan_batch_host(s, data, sizes, n);
+  const yr_amd_match_rec* d_m = nullptr;
+  const yr_amd_verify_rec* d_r = nullptr;
+  const uint64_t *mo = nullptr, *ro = nullptr;
+  if (!r) r = yr_amd_match_batch_device(s, bases, &d_m, &mo, &d_r, &ro);
+  if (r) return r;
+  const uint64_t nm = mo[n], nr = ro[n];
+  s->h_match.resize(nm);
+  s->h_mrest.resize(nr);
+  if (nm > 0)
+    HIP_TRY(hipMemcpyAsync(s->h_match.data(), d_m, nm * sizeof(yr_amd_match_rec),
+                           hipMemcpyDeviceToHost, s->stream));
+  if (nr > 0)
+    HIP_TRY(hipMemcpyAsync(s->h_mrest.data(), d_r, nr * sizeof(yr_amd_verify_rec),
+                           hipMemcpyDeviceToHost, s->stream));
+  if (nm > 0 || nr > 0) HIP_TRY(hipStreamSynchronize(s->stream));
+  if (matches) *matches = s->h_match.data();
+  if (match_off) *match_off = mo;
+  if (rest) *rest = s->h_mrest.data();
+  if (rest_off) *rest_off = ro;
+  return YR_AMD_SUCCESS;
 }
 
 int yr_amd_trace_walk(yr_amd_scanner* s, const uint8_t* d_data, size_t size, uint64_t data_base,
