@@ -552,6 +552,60 @@ int yr_amd_scan_block_matches(
     uint64_t* n_rest);
 
 /*
+ * ---- Final matches of hex strings on the device (opt-in) ----
+ *
+ * The match stage settles the strings of the scanner's CLASSES.  The default,
+ * YR_AMD_MATCH_LITERAL, is the final strings above.  YR_AMD_MATCH_HEX adds the
+ * FINAL HEX strings: flags with STRING_FLAGS_FAST_REGEXP (0x40, set by the hex
+ * lexer alone) and STRING_FLAGS_ASCII (0x08), and none of LITERAL (0x400),
+ * CHAIN_PART (0x2000), WIDE (0x10), NO_CASE (0x04), FULL_WORD (0x80),
+ * GREEDY_REGEXP (0x10000), BASE64 (0x200000), BASE64_WIDE (0x400000).  (A hex
+ * string without wildcards or jumps is LITERAL and final already; the other
+ * excluded flags do not occur on a compiler-made hex string.)
+ *
+ * A record (pool entry, offset) of such a string is measured as
+ * _yr_scan_verify_re_match + yr_re_fast_exec do (scan.c:778-885,
+ * re.c:2150-2423): the forward program from data + offset gives F, the
+ * smallest bytes_matched at RE_OPCODE_MATCH; without a backward program the
+ * match is (offset, F), none if F == 0; with one, every bytes_matched value B
+ * of its exhaustive run gives a match (offset - B, B + F) -- so one record can
+ * be several matches.  xor_key is 0.  Across records the rule above holds:
+ * one entry per distinct (string, offset), the first record in record order
+ * supplying length and pool_index.
+ *
+ * The device keeps the set of bytes_matched values in a 64-position window.
+ * A record it cannot measure exactly -- a set wider than that or within reach
+ * of YR_RE_SCAN_LIMIT, a pool entry without forward program, after
+ * yr_amd_scan_window a byte either run may read outside the window -- goes to
+ * the rest unchanged, never out as a guess.  YR_MAX_STRING_MATCHES,
+ * SCAN_FLAGS_FAST_MODE / STRING_FLAGS_SINGLE_MATCH and temporarily disabled
+ * strings are host state and not applied, as for literals.
+ *
+ * yr_amd_scanner_set_match_classes: the LITERAL bit must stay set;
+ * YR_AMD_INVALID_ARGUMENT otherwise and for unknown bits.  With HEX set,
+ * yr_amd_match_device and yr_amd_scan_block_matches need the strings'
+ * programs (yr_amd_tables_set_re_code; yr_amd_tables_load_yarc attaches them
+ * itself) and return YR_AMD_INVALID_ARGUMENT without; more than
+ * YR_AMD_MATCH_MAX_RECORDS matches-to-be are refused likewise.  The batch
+ * calls (yr_amd_match_batch_device, yr_amd_scan_batch_matches) ignore the
+ * setting and stay literal-only: their CSR offsets rely on every buffer
+ * keeping its slot range through the sort, which records that expand into
+ * several entries do not.
+ *
+ * yr_amd_tables_match_strings: out[k] = 1 iff string k is in one of the
+ * classes.  Host code with the preconditions of yr_amd_tables_final_strings,
+ * which it equals for classes = YR_AMD_MATCH_LITERAL; classes as above.
+ */
+#define YR_AMD_MATCH_LITERAL 1u
+#define YR_AMD_MATCH_HEX 2u
+int yr_amd_scanner_set_match_classes(yr_amd_scanner* scanner, uint32_t classes);
+int yr_amd_tables_match_strings(
+    const yr_amd_tables* tables,
+    uint32_t classes,
+    uint8_t* out,
+    uint32_t n_strings);
+
+/*
  * ---- Batched scans: many independent buffers in one launch ----
  *
  * Every call above takes one block and pays its fixed cost -- a scan launch in

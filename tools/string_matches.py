@@ -1,6 +1,6 @@
 """Which literal strings of a compiled rules file match where in a file.
 
-    python tools/string_matches.py RULES.yarc FILE [FILE ...]
+    python tools/string_matches.py [--hex] RULES.yarc FILE [FILE ...]
 
 Prints one "string offset length xor" line per match of a final string
 (include/yara_amd.h: literal, not a chain part, not base64) -- absolute file
@@ -26,6 +26,13 @@ one scan, one pre-verification and one match stage for all files of an arena
 split across several arenas when needed; every such file is one buffer, so
 its lines are those of a stock scan of the file.  A larger file takes the
 block path above.
+
+--hex: the final hex strings too (YR_AMD_MATCH_HEX: hex strings with wildcards
+or jumps that are no chain parts), measured on the GPU as yr_re_fast_exec does;
+a call of one can be several matches.  The calls left are then those of
+regexps, chain parts and base64 strings (and hex calls whose jumps span more
+than 64 positions).  The batch calls are literal-only, so with --hex every file
+takes the block path.
 """
 import gzip
 import os
@@ -75,15 +82,19 @@ def arenas(sizes):
 
 
 def main():
-    if len(sys.argv) < 3:
+    argv = [a for a in sys.argv[1:] if a != "--hex"]
+    hex_class = len(argv) != len(sys.argv) - 1
+    if len(argv) < 2:
         sys.exit(__doc__)
     import numpy as np
     import yara_amd
-    opener = gzip.open if sys.argv[1].endswith(".gz") else open
-    with opener(sys.argv[1], "rb") as f:
+    opener = gzip.open if argv[0].endswith(".gz") else open
+    with opener(argv[0], "rb") as f:
         tables = yara_amd.Tables.from_yarc(f.read(), device=0)
     sc = yara_amd.Scanner(tables)
-    paths = sys.argv[2:]
+    if hex_class:
+        sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+    paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))
         for r in matches:
@@ -92,7 +103,7 @@ def main():
         return
     sizes = [os.path.getsize(p) for p in paths]
     per, left = [None] * len(paths), 0
-    for group in arenas(sizes):
+    for group in ([] if hex_class else arenas(sizes)):
         try:
             m, mo, rest, _ = sc.batch_string_matches(
                 [np.fromfile(paths[k], dtype=np.uint8) for k in group])
@@ -104,7 +115,7 @@ def main():
             per[k] = m[int(mo[j]):int(mo[j + 1])]
         left += len(rest)
     for k, p in enumerate(paths):
-        if per[k] is None:   # larger than BLOCK
+        if per[k] is None:   # larger than BLOCK, or --hex
             per[k], n = block_path(sc, np.fromfile(p, dtype=np.uint8))
             left += n
         for r in per[k]:

@@ -20,11 +20,11 @@ import numpy as np
 
 from . import _lib
 from ._lib import (CALLBACK_ERROR, COULD_NOT_MAP_FILE, INSUFFICIENT_MEMORY,  # noqa: F401
-                   INTERNAL_FATAL_ERROR, INVALID_ARGUMENT, MAX_ATOM_LENGTH, SCAN_TIMEOUT, SUCCESS,
-                   YaraAmdError)
+                   INTERNAL_FATAL_ERROR, INVALID_ARGUMENT, MATCH_HEX, MATCH_LITERAL,
+                   MAX_ATOM_LENGTH, SCAN_TIMEOUT, SUCCESS, YaraAmdError)
 
 __all__ = ["Tables", "Scanner", "Pipeline", "replay", "fill_xorshift64", "version",
-           "batch_layout", "merge_matches", "YaraAmdError"]
+           "batch_layout", "merge_matches", "YaraAmdError", "MATCH_LITERAL", "MATCH_HEX"]
 
 
 def _arr(a, dt):
@@ -188,6 +188,16 @@ class Tables:
             self._h, out.ctypes.data_as(_lib._u8p), n))
         return out[:n].astype(bool)
 
+    def match_strings(self, classes: int = MATCH_LITERAL):
+        """bool[n_strings]: the strings the match stage settles with these
+        classes (yr_amd_tables_match_strings): MATCH_LITERAL is final_strings,
+        MATCH_LITERAL | MATCH_HEX adds the final hex strings."""
+        n = self.string_count()
+        out = np.zeros(max(n, 1), np.uint8)
+        _lib.check("yr_amd_tables_match_strings", _lib.lib().yr_amd_tables_match_strings(
+            self._h, classes, out.ctypes.data_as(_lib._u8p), n))
+        return out[:n].astype(bool)
+
     def set_profiling(self, enable: bool = True):
         """Count-only records for libyara's profiling counters
         (yr_amd_tables_set_profiling)."""
@@ -258,6 +268,7 @@ class Scanner:
         self._h = h
         self.tables = tables
         self._batch_n = 0   # buffers of the last scan_batch_device
+        self._classes = MATCH_LITERAL   # set_match_classes
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -322,15 +333,41 @@ class Scanner:
                                                    ctypes.byref(cnt)))
         return p.value or 0, cnt.value
 
-    # -- final matches of literal strings --------------------------------------
-    def match_device(self, data_base: int = 0):
+    # -- final matches of literal (and, opted in, hex) strings -------------------
+    def set_match_classes(self, classes: int):
+        """The string classes the match stage settles
+        (yr_amd_scanner_set_match_classes): MATCH_LITERAL (the default), or
+        MATCH_LITERAL | MATCH_HEX.  The batch calls stay literal-only."""
+        _lib.check("yr_amd_scanner_set_match_classes",
+                   _lib.lib().yr_amd_scanner_set_match_classes(self._h, classes))
+        self._classes = classes
+
+    def _with_hex(self, hex, call):
+        # hex=True: this call with the hex class added, the scanner's setting restored
+        was = self._classes
+        if not hex or (was & MATCH_HEX):
+            return call()
+        self.set_match_classes(was | MATCH_HEX)
+        try:
+            return call()
+        finally:
+            self.set_match_classes(was)
+
+    def match_device(self, data_base: int = 0, hex: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
         copied to the host: ``matches`` {offset, string, length, xor_key,
         pool_index}, one per distinct (string, offset) of the final strings
         (Tables.final_strings), ascending by (string, offset), block-local
         offsets; ``rest`` {offset, pool_index, candidate}, the verify calls a
         host verifier still has to make, in call order.  A block of more than
-        2^32 bytes (a window of one too) is refused: INVALID_ARGUMENT."""
+        2^32 bytes (a window of one too) is refused: INVALID_ARGUMENT.
+        ``hex=True`` settles the final hex strings too for this call
+        (Tables.match_strings(MATCH_LITERAL | MATCH_HEX)): a call of one can
+        be several matches; ``hex=False`` leaves the scanner's classes
+        (set_match_classes) as they are."""
+        return self._with_hex(hex, lambda: self._match_device(data_base))
+
+    def _match_device(self, data_base):
         from ._hip import memcpy
         pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
         nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
@@ -345,11 +382,14 @@ class Scanner:
             memcpy(rest.ctypes.data, pr.value, nr.value * 16, 2)
         return matches, rest
 
-    def string_matches(self, data: np.ndarray, data_base: int = 0):
+    def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False):
         """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
         see match_device.  For the final strings ``matches`` is what stock
         libyara's match lists hold after scanning this block alone; the blocks
         of one scan merge with ``merge_matches``."""
+        return self._with_hex(hex, lambda: self._string_matches(data, data_base))
+
+    def _string_matches(self, data, data_base):
         d = _arr(data, np.uint8)
         pm = ctypes.POINTER(_lib.MatchRec)()
         pr = ctypes.POINTER(_lib.VerifyRec)()

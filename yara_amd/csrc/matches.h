@@ -1,4 +1,4 @@
-// Device data of the final-match stage for literal strings (matches.hip).
+// Device data of the final-match stage for literal and hex strings (matches.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +17,27 @@ constexpr uint32_t kStrChainPart = 0x2000;   // STRING_FLAGS_CHAIN_PART (types.h
 // comparison the device does not restate).
 __host__ __device__ inline bool string_is_final(uint32_t flags) {
   return (flags & kStrLiteral) != 0 && (flags & (kStrChainPart | kStrBase64Any)) == 0;
+}
+
+// The classes of strings the match stage settles (include/yara_amd.h
+// YR_AMD_MATCH_*).
+constexpr uint32_t kMatchLiteral = 1u, kMatchHex = 2u;
+constexpr uint32_t kStrGreedyRegexp = 0x10000;   // STRING_FLAGS_GREEDY_REGEXP
+
+// A FINAL HEX string: yr_re_fast_exec programs (only the hex lexer sets
+// FAST_REGEXP) run on the plain ascii form.  _yr_scan_verify_re_match
+// (scan.c:778-885) hands every backward MATCH of such a call to
+// _yr_scan_add_match_to_list; the device restates both runs in position-set
+// form (matches.hip hex_run).  The excluded flags do not occur on a
+// compiler-made hex string: a hand-made table with one falls to the rest.
+__host__ __device__ inline bool string_is_final_hex(uint32_t flags) {
+  return (flags & (kStrFastRegexp | kStrAscii)) == (kStrFastRegexp | kStrAscii) &&
+         (flags & (kStrLiteral | kStrChainPart | kStrWide | kStrNoCase | kStrFullWord |
+                   kStrGreedyRegexp | kStrBase64Any)) == 0;
+}
+__host__ __device__ inline bool string_in_classes(uint32_t flags, uint32_t classes) {
+  return ((classes & kMatchLiteral) && string_is_final(flags)) ||
+         ((classes & kMatchHex) && string_is_final_hex(flags));
 }
 
 // Same layout as yr_amd_match_rec (include/yara_amd.h).
@@ -109,5 +130,46 @@ hipError_t batch_match_sort(uint64_t* const keys[2], uint32_t* const index[2], u
 // As launch_match_unique; an entry is kept iff it is a match and its (buffer,
 // key) differs from its predecessor's.
 hipError_t launch_batch_match_unique(const BatchMatchParams& p, int pass, hipStream_t s);
+
+// ---- The stage with the hex class (yr_amd_scanner_set_match_classes) ----
+// A record of a final hex string can be several matches: one per
+// bytes_matched value B of the backward program at MATCH, at offset - B with
+// length B + F (F the forward program's smallest).  Records become ITEMS, one
+// per match to be, and the sort and the unique pass work on items.  What a
+// record contributes is its set of B values, a 64-bit mask over [base, base +
+// 64); a literal record's set is {0}.
+struct HexSet {
+  uint64_t mask;   // bit i: B = base + i
+  uint32_t base;
+  uint32_t pad;
+};
+
+// A struct of its own: MatchParams is a kernel argument of the literal-only
+// kernels, which stay what they are.  m.keys / m.block_off / m.chunk_off /
+// m.rest are per RECORD here (the key of a record that yields no item has the
+// string field n_strings: match_rest_kernel reads exactly that); the items'
+// arrays are ikeys / iindex, and m.sorted_* / m.out hold items.
+struct HexMatchParams {
+  MatchParams m;
+  const uint8_t* re_code;
+  uint32_t classes;
+  HexSet* sets;                 // [m.n] by record
+  uint64_t* iblock_off;         // [verify_groups(m.n) + 1] items per wave of records -> offsets
+  uint64_t* ichunk_off;         // [verify_chunks(m.n) + 1]
+  uint64_t n_items;             // (expand, unique: after the wait for the count)
+  uint64_t* ikeys;              // [n_items] string << 32 | (offset - B), records ascending
+  uint32_t* iindex;             // [n_items] the item's record
+  uint64_t* ublock_off;         // [verify_groups(n_items) + 1] unique pass
+  uint64_t* uchunk_off;
+};
+
+// Measure: per record its key, measure, set; per wave the rest records into
+// m.block_off and the items into iblock_off.
+hipError_t launch_hex_measure(const HexMatchParams& p, hipStream_t s);
+// The items of every record at its offset (iblock_off / ichunk_off scanned).
+hipError_t launch_hex_expand(const HexMatchParams& p, hipStream_t s);
+// As launch_match_unique over the items: the length is the record's forward
+// length plus the distance from the item's offset to the record's.
+hipError_t launch_hex_unique(const HexMatchParams& p, int pass, hipStream_t s);
 
 }  // namespace yamd

@@ -26,6 +26,11 @@
 //   3. match_unique_kernel: an entry is kept iff its key differs from its
 //      predecessor's; kept entries are compacted in order into MatchRec.
 //
+// With the hex class (yr_amd_scanner_set_match_classes) a record of a final
+// hex string is measured too and can be several matches: hex_measure_kernel,
+// hex_expand_kernel and hex_unique_kernel below take the place of 1. and 3.,
+// the sort runs over the items (matches.h HexMatchParams).
+//
 // The comparisons are restated here rather than shared with verify.hip: that
 // file's kernels stay byte for byte what they were (their register budgets are
 // tuned), and these read global memory directly -- a
@@ -407,6 +412,269 @@ __global__ __launch_bounds__(256) void batch_match_offsets_kernel(BatchMatchPara
   (MATCHES ? p.match_off : p.rest_off)[k] = o;
 }
 
+// ---- The stage with the hex class (matches.h HexMatchParams) ----
+
+// Regexp code from the blob in global memory or from this lane's LDS copy
+// (verify.hip's two readers, restated).
+struct GlobalCode {
+  const uint8_t* __restrict__ p;
+  __device__ uint8_t operator[](uint32_t i) const { return p[i]; }
+};
+struct LdsCode {
+  uint32_t a;   // LDS byte address
+  __device__ uint8_t operator[](uint32_t i) const {
+    return *reinterpret_cast<const __attribute__((address_space(3))) uint8_t*>((uintptr_t)(a + i));
+  }
+};
+constexpr uint32_t kHexCodeBytes = 48;   // LDS per lane: three aligned 16-byte loads
+constexpr uint32_t kNoLds = 0xFFFFFFFFu;
+
+// verify.hip stage_code: a program that fits goes into this lane's LDS with
+// three independent loads (the blob carries 64 bytes of padding).
+__device__ __forceinline__ uint32_t hex_stage_code(const uint8_t* code, uint32_t len, uint32_t buf) {
+  const uintptr_t a = (uintptr_t)code, lo = a & ~(uintptr_t)15;
+  const uint32_t head = (uint32_t)(a - lo);
+  if (head + len > kHexCodeBytes) return kNoLds;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4* g = reinterpret_cast<const u32x4*>(lo);
+  const u32x4 c0 = g[0], c1 = g[1], c2 = g[2];
+  typedef __attribute__((address_space(3))) u32x4 lds_u4;
+  lds_u4* d = reinterpret_cast<lds_u4*>((uintptr_t)buf);
+  d[0] = c0;
+  d[1] = c1;
+  d[2] = c2;
+  return buf + head;
+}
+
+constexpr int kHexNone = 0, kHexMatch = 1, kHexUndecided = 2;
+
+// yr_re_fast_exec (re.c:2150-2423) in position-set form, verify.hip
+// fast_re_set's transitions, but with the set at RE_OPCODE_MATCH as the
+// result: bit i of out.mask = bytes_matched value out.base + i.  Byte b of the
+// input is input[b], backwards input[-1 - b]; only live positions (b < maxb)
+// are read, so no byte outside the block.  kHexUndecided: the set would leave
+// the 64-position window or come near YR_RE_SCAN_LIMIT, an opcode outside the
+// fast set, a program that does not end in MATCH, or a REPEAT_ANY right
+// before MATCH (whose b + min the reference does not bound).
+template <class Code>
+__device__ int hex_run(const Code code, uint32_t len, const uint8_t* __restrict__ input, int maxb,
+                       bool backwards, HexSet& out) {
+  int base = 0;
+  uint64_t m = 1;
+  uint32_t ip = 0;
+  while (ip < len) {
+    const uint8_t op = code[ip], b1 = code[ip + 1], b2 = code[ip + 2];
+    if (op == kReMatch) {
+      out.mask = m;
+      out.base = (uint32_t)base;
+      return kHexMatch;   // (m != 0: every transition below returns on an empty set)
+    }
+    const int lim = maxb - base;   // bits i < lim are live (b < max_bytes_matched)
+    const uint64_t live = lim >= 64 ? m : (lim <= 0 ? 0ull : m & ((1ull << lim) - 1));
+    if (live == 0) return kHexNone;
+    if (op == kReRepeatAnyUngreedy) {
+      const int mn = b1 | (b2 << 8);
+      const int mx = code[ip + 3] | (code[ip + 4] << 8);
+      if (mx < mn || code[ip + 5] == kReMatch) return kHexUndecided;
+      const int lo = __builtin_ctzll(live), hi = 63 - __builtin_clzll(live);
+      const int span = hi - lo + (mx - mn);
+      const int nb = base + lo + mn;
+      if (span > 63 || nb + span >= kReScanLimit) return kHexUndecided;
+      // t | t << 1 | ... | t << (mx - mn), by doubling
+      uint64_t acc = live >> lo;
+      const int r = mx - mn + 1;   // copies
+      int have = 1;
+      while (2 * have <= r) {
+        acc |= acc << have;
+        have *= 2;
+      }
+      if (have < r) acc |= acc << (r - have);
+      // (b + min at or past maxb dies at the next, consuming, opcode)
+      const int lim2 = maxb - nb;
+      acc &= lim2 >= 64 ? ~0ull : (lim2 <= 0 ? 0ull : (1ull << lim2) - 1);
+      if (acc == 0) return kHexNone;
+      m = acc;
+      base = nb;
+      ip += 5;
+      continue;
+    }
+    uint32_t mask, val, sz;
+    bool neg = false;
+    switch (op) {
+      case kReAny: mask = 0; val = 0; sz = 1; break;
+      case kReLiteral: mask = 0xFF; val = b1; sz = 2; break;
+      case kReNotLiteral: mask = 0xFF; val = b1; sz = 2; neg = true; break;
+      case kReMaskedLiteral: mask = b2; val = b1; sz = 3; break;
+      case kReMaskedNotLiteral: mask = b2; val = b1; sz = 3; neg = true; break;
+      default: return kHexUndecided;
+    }
+    uint64_t res = 0, x = live;
+    while (x) {   // live positions only (never past the block)
+      const int i = __builtin_ctzll(x);
+      const int b = base + i;
+      const uint8_t c = backwards ? input[-1 - b] : input[b];
+      res |= (uint64_t)((((uint32_t)c & mask) == val) != neg) << i;
+      x &= x - 1;
+    }
+    if (res == 0) return kHexNone;
+    m = res;
+    base += 1;
+    ip += sz;
+  }
+  return kHexUndecided;
+}
+
+// _yr_scan_verify_re_match (scan.c:778-885) of a final hex string's record:
+// kHexMatch with m.length = F, the forward program's smallest bytes_matched,
+// and the backward program's set in `set` ({0} without one).
+template <class Code>
+__device__ int hex_call(const MatchParams& p, const DevRe& r, const Code fwd, const Code bwd,
+                        uint64_t offset, MatchMeasure& m, HexSet& set) {
+  const uint8_t* d = p.data + offset;
+  HexSet f;
+  int v = hex_run(fwd, r.fwd_len, d, (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit),
+                  false, f);
+  if (v != kHexMatch) return v;
+  m.length = f.base + (uint32_t)__builtin_ctzll(f.mask);   // the first of the ascending list
+  if (r.bwd_len == 0) return m.length != 0 ? kHexMatch : kHexNone;
+  return hex_run(bwd, r.bwd_len, d, (int)min<uint64_t>(offset, (uint64_t)kReScanLimit), true, set);
+}
+
+__device__ int measure_hex(const HexMatchParams& q, const DevPoolRec& e, uint64_t offset,
+                           uint32_t codebuf, MatchMeasure& m, HexSet& set) {
+  const MatchParams& p = q.m;
+  if (offset >= p.size) return kHexNone;
+  // (measure()'s bounds: every byte either run may read)
+  if (p.win_lo != 0 || p.win_hi != p.size) {
+    const uint64_t need_lo = offset - min<uint64_t>(offset, (uint64_t)kReScanLimit);
+    const uint64_t need_hi =
+        min<uint64_t>(p.size, offset + max<uint64_t>((uint64_t)kReScanLimit, 2ull * e.length + 2));
+    if (need_lo < p.win_lo || need_hi > p.win_hi) return kHexUndecided;
+  }
+  const DevRe r = e.re;
+  if (r.fwd_len == 0) return kHexUndecided;
+  const uint8_t* fwd = q.re_code + r.fwd_off;
+  const uint8_t* bwd = q.re_code + r.bwd_off;
+  // (contiguous in the blob: both programs staged at once when they fit)
+  if (r.bwd_len == 0 || r.bwd_off == r.fwd_off + r.fwd_len) {
+    const uint32_t at = hex_stage_code(fwd, r.fwd_len + r.bwd_len, codebuf);
+    if (at != kNoLds) return hex_call(p, r, LdsCode{at}, LdsCode{at + r.fwd_len}, offset, m, set);
+  }
+  return hex_call(p, r, GlobalCode{fwd}, GlobalCode{bwd}, offset, m, set);
+}
+
+// The inclusive prefix sum of v over the wave's lanes.
+__device__ __forceinline__ uint32_t wave_prefix(uint32_t v) {
+  const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t t = (uint32_t)__shfl_up((int)v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t hex_items(uint64_t key, uint32_t n_strings, const HexSet& s) {
+  return (uint32_t)(key >> 32) == n_strings ? 0u : (uint32_t)__popcll(s.mask);
+}
+
+__global__ __launch_bounds__(256) void hex_measure_kernel(HexMatchParams q) {
+  // one code buffer per lane, + the operand bytes an opcode's read may reach
+  // past the last lane's program
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const MatchParams& p = q.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool rest = false;
+  uint32_t items = 0;
+  if (r < p.n) {
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      // (the low 32 bits of a flat LDS address are the LDS offset)
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      // (a record the runs find nothing for is not dropped here: the host
+      // verifies it and finds what there is)
+      is_match = measure_hex(q, e, rec.offset, buf, m, set) == kHexMatch;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(p, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? p.pool_string[rec.pool_index] : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    q.sets[r] = set;
+    rest = !is_match;
+    items = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  const uint64_t mask = __ballot(rest);
+  const uint32_t total = (uint32_t)__shfl((int)wave_prefix(items), 63, 64);
+  if ((threadIdx.x & 63u) == 0 && r < p.n) {
+    p.block_off[r / kGroup] = (uint64_t)__popcll(mask);
+    q.iblock_off[r / kGroup] = (uint64_t)total;
+  }
+}
+
+// One lane per record: its items at the wave's offset plus the counts of the
+// lanes below.  Records ascend in the item array, so the stable sort keeps
+// "the first record of a (string, offset) wins".
+__global__ __launch_bounds__(256) void hex_expand_kernel(HexMatchParams q) {
+  const MatchParams& p = q.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t key = 0;
+  HexSet set{0ull, 0u, 0u};
+  uint32_t items = 0;
+  if (r < p.n) {
+    key = p.keys[r];
+    set = q.sets[r];
+    items = hex_items(key, p.n_strings, set);
+  }
+  const uint32_t before = wave_prefix(items) - items;
+  if (items == 0) return;
+  const uint64_t g = r / kGroup;
+  uint64_t at = q.ichunk_off[g / kChunkGroups] + q.iblock_off[g] + before;
+  const uint64_t offset = key & 0xFFFFFFFFull;   // (B <= min(offset, YR_RE_SCAN_LIMIT))
+  for (uint64_t x = set.mask; x != 0 && at < q.n_items; x &= x - 1, ++at) {
+    const uint32_t B = set.base + (uint32_t)__builtin_ctzll(x);
+    q.ikeys[at] = (key & 0xFFFFFFFF00000000ull) | (offset - B);
+    q.iindex[at] = (uint32_t)r;
+  }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void hex_unique_kernel(HexMatchParams q) {
+  const MatchParams& p = q.m;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  uint64_t key = 0;
+  if (i < q.n_items) {
+    key = p.sorted_keys[i];
+    keep = (uint32_t)(key >> 32) < p.n_strings && (i == 0 || p.sorted_keys[i - 1] != key);
+  }
+  const uint64_t mask = __ballot(keep);
+  if (PASS == 0) {
+    if ((threadIdx.x & 63u) == 0 && i < q.n_items)
+      q.ublock_off[i / kGroup] = (uint64_t)__popcll(mask);
+    return;
+  }
+  if (!keep) return;
+  const uint32_t r = p.sorted_index[i];   // the first record with this (string, offset)
+  const MatchMeasure m = p.meas[r];
+  const VerifyRec rec = p.recs[r];
+  MatchRec o;
+  o.offset = key & 0xFFFFFFFFull;
+  o.string = (uint32_t)(key >> 32);
+  // B + F: B is how far the item lies before its record's offset
+  o.length = m.length + (uint32_t)((rec.offset & 0xFFFFFFFFull) - o.offset);
+  o.xor_key = m.xor_key;
+  o.pool_index = rec.pool_index;
+  const uint64_t g = i / kGroup;
+  p.out[q.uchunk_off[g / kChunkGroups] + q.ublock_off[g] + lanes_below(mask)] = o;
+}
+
 }  // namespace
 
 hipError_t launch_match_classify(const MatchParams& p, hipStream_t s) {
@@ -462,6 +730,29 @@ hipError_t launch_match_unique(const MatchParams& p, int pass, hipStream_t s) {
     hipLaunchKernelGGL(match_unique_kernel<0>, match_grid(p.n), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(match_unique_kernel<1>, match_grid(p.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_hex_measure(const HexMatchParams& p, hipStream_t s) {
+  if (p.m.n == 0 || p.m.n > kMatchMaxRecords) return p.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(hex_measure_kernel, match_grid(p.m.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_hex_expand(const HexMatchParams& p, hipStream_t s) {
+  if (p.m.n == 0 || p.n_items == 0) return hipSuccess;
+  if (p.m.n > kMatchMaxRecords || p.n_items > kMatchMaxRecords) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hex_expand_kernel, match_grid(p.m.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_hex_unique(const HexMatchParams& p, int pass, hipStream_t s) {
+  if (p.n_items == 0 || p.n_items > kMatchMaxRecords)
+    return p.n_items == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (pass == 0)
+    hipLaunchKernelGGL(hex_unique_kernel<0>, match_grid(p.n_items), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(hex_unique_kernel<1>, match_grid(p.n_items), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

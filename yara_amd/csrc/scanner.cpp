@@ -226,7 +226,7 @@ struct yr_amd_scanner {
   size_t mhist_cap = 0;
   uint64_t* d_mhchunk = nullptr;
   size_t mhchunk_cap = 0;
-  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch}
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items}
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
@@ -236,6 +236,21 @@ struct yr_amd_scanner {
   uint64_t* d_moff = nullptr;           // [2 * (n + 1)]: match_off, rest_off
   size_t moff_cap = 0;
   std::vector<uint64_t> h_match_off, h_mrest_off;
+  // the stage with the hex class (yr_amd_scanner_set_match_classes; matches.h
+  // HexMatchParams): the arrays by RECORD -- the workspace above then holds items
+  uint32_t match_classes = kMatchLiteral;
+  uint64_t* d_hkeys = nullptr;          // [cap] the records' keys
+  size_t hkeys_cap = 0;
+  MatchMeasure* d_hmeas = nullptr;      // [cap]
+  size_t hmeas_cap = 0;
+  HexSet* d_hsets = nullptr;            // [cap]
+  size_t hsets_cap = 0;
+  VerifyRec* d_hrest = nullptr;         // [cap]
+  size_t hrest_cap = 0;
+  uint64_t* d_hblock = nullptr;         // [2 * (groups + 1)]: rest records, items per wave
+  size_t hblock_cap = 0;
+  uint64_t* d_hchunk = nullptr;         // [2 * (chunks + 1)]
+  size_t hchunk_cap = 0;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -531,7 +546,9 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_bunit, (void*)s->d_bunit_off, (void*)s->d_gather,
                   (void*)s->d_mkeys, (void*)s->d_mindex, (void*)s->d_mmeas, (void*)s->d_mrest,
                   (void*)s->d_mout, (void*)s->d_mblock, (void*)s->d_mchunk, (void*)s->d_mhist,
-                  (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff})
+                  (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff, (void*)s->d_hkeys,
+                  (void*)s->d_hmeas, (void*)s->d_hsets, (void*)s->d_hrest, (void*)s->d_hblock,
+                  (void*)s->d_hchunk})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1711,7 +1728,7 @@ int reallocate(T*& p, size_t need) {
 // two CSR offset arrays too.
 int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (s->h_msum == nullptr) {
-    if (hipHostMalloc((void**)&s->h_msum, 3 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
+    if (hipHostMalloc((void**)&s->h_msum, 4 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
       s->h_msum = nullptr;
       return YR_AMD_INSUFFICIENT_MEMORY;
     }
@@ -1743,8 +1760,109 @@ int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (!r && nbuf > 0) r = grow_geo(s->d_moff, s->moff_cap, 2 * ((size_t)nbuf + 1));
   return r;
 }
+
+// The stage with the hex class: records -> items -> matches (matches.h
+// HexMatchParams).  Two waits: the item count sizes the sort's workspace.
+int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n, uint64_t* nm,
+                     uint64_t* nr) {
+  const yr_amd_tables* t = s->tables;
+  const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
+  int r = ensure_match_workspace(s, 1);   // (the pinned totals; the items' arrays grow below)
+  if (!r) r = grow_geo(s->d_hkeys, s->hkeys_cap, n);
+  if (!r) r = grow_geo(s->d_hmeas, s->hmeas_cap, n);
+  if (!r) r = grow_geo(s->d_hsets, s->hsets_cap, n);
+  if (!r) r = grow_geo(s->d_hrest, s->hrest_cap, n);
+  if (!r) r = grow_geo(s->d_hblock, s->hblock_cap, 2 * groups);
+  if (!r) r = grow_geo(s->d_hchunk, s->hchunk_cap, 2 * chunks);
+  if (r) return r;
+  HexMatchParams p{};
+  p.m.data = s->last.data;
+  p.m.size = s->last.block_size;
+  p.m.win_lo = s->win_lo;
+  p.m.win_hi = s->win_hi;
+  p.m.recs = reinterpret_cast<const VerifyRec*>(d_rec);
+  p.m.n = n;
+  p.m.pool = t->d_pool;
+  p.m.pool_string = t->d_pool_string;
+  p.m.n_strings = (uint32_t)t->h_str_flags.size();
+  p.m.str_bytes = t->d_str_bytes;
+  p.m.lowercase = t->d_lowercase;
+  p.m.keys = s->d_hkeys;
+  p.m.meas = s->d_hmeas;
+  p.m.block_off = s->d_hblock;
+  p.m.chunk_off = s->d_hchunk;
+  p.m.rest = s->d_hrest;
+  p.re_code = t->d_re_code;
+  p.classes = s->match_classes;
+  p.sets = s->d_hsets;
+  p.iblock_off = s->d_hblock + groups;
+  p.ichunk_off = s->d_hchunk + chunks;
+  const KeptLists none{{0, 0, 0, 0}};
+  // measure -> the offsets of the rest and of the items -> the rest; wait
+  HIP_TRY(launch_hex_measure(p, s->stream));
+  HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
+  HIP_TRY(launch_block_offsets(p.iblock_off, p.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
+                               s->stream));
+  HIP_TRY(launch_match_rest(p.m, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *nr = s->h_msum[0];
+  const uint64_t items = s->h_msum[3];
+  if (*nr > n || items > 64 * (n - *nr)) return YR_AMD_INTERNAL_FATAL_ERROR;
+  if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
+  *nm = 0;
+  if (items == 0) return YR_AMD_SUCCESS;
+  r = ensure_match_workspace(s, items);
+  if (r) return r;
+  p.n_items = items;
+  p.ikeys = s->d_mkeys;
+  p.iindex = s->d_mindex;
+  p.ublock_off = s->d_mblock;
+  p.uchunk_off = s->d_mchunk;
+  p.m.out = s->d_mout;
+  // the offsets only decrease (offset - B): the same varying bits
+  int lo_bits = 1, hi_bits = 1;
+  while (lo_bits < 32 && ((p.m.size - 1) >> lo_bits) != 0) ++lo_bits;
+  while (hi_bits < 32 && (p.m.n_strings >> hi_bits) != 0) ++hi_bits;
+  uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+  uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+  // expand; sort; distinct keys -> their offsets -> the matches; wait
+  HIP_TRY(launch_hex_expand(p, s->stream));
+  int sorted = 0;
+  HIP_TRY(match_sort(keys, index, items, lo_bits, hi_bits, s->d_mhist, s->d_mhchunk, s->d_mhsum + 2,
+                     s->stream, &sorted));
+  p.m.sorted_keys = keys[sorted];
+  p.m.sorted_index = index[sorted];
+  HIP_TRY(launch_hex_unique(p, 0, s->stream));
+  HIP_TRY(launch_block_offsets(p.ublock_off, p.uchunk_off, items, s->d_mhsum + 1, nullptr, none,
+                               s->stream));
+  HIP_TRY(launch_hex_unique(p, 1, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *nm = s->h_msum[1];
+  if (*nm > items) return YR_AMD_INTERNAL_FATAL_ERROR;
+  return YR_AMD_SUCCESS;
+}
 }  // namespace
 }  // extern "C++"
+
+int yr_amd_scanner_set_match_classes(yr_amd_scanner* s, uint32_t classes) {
+  if (s == nullptr || !(classes & YR_AMD_MATCH_LITERAL) ||
+      (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
+    return YR_AMD_INVALID_ARGUMENT;
+  s->match_classes = classes;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_tables_match_strings(const yr_amd_tables* t, uint32_t classes, uint8_t* out,
+                                uint32_t n_strings) {
+  if (t == nullptr || !(t->has_strings || t->has_str_flags) || n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && out == nullptr))
+    return YR_AMD_INVALID_ARGUMENT;
+  if (!(classes & YR_AMD_MATCH_LITERAL) || (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_strings; ++k)
+    out[k] = string_in_classes(t->h_str_flags[k], classes) ? 1 : 0;
+  return YR_AMD_SUCCESS;
+}
 
 int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_match_rec** d_matches,
                         uint64_t* n_matches, const yr_amd_verify_rec** d_rest, uint64_t* n_rest) {
@@ -1757,13 +1875,19 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
   // candidate count, not the size, so a larger block is refused here.
   if (s->last.block_size > YR_AMD_MATCH_MAX_BLOCK) return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_tables* t = s->tables;
+  // the hex class interprets the strings' programs (yr_amd_tables_set_re_code)
+  const bool hex = (s->match_classes & kMatchHex) != 0;
+  if (hex && t->d_re_code == nullptr) return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_verify_rec* d_rec = nullptr;
   uint64_t n = 0;
   int r = yr_amd_verify_device(s, data_base, &d_rec, &n);
   if (r) return r;
   if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   uint64_t nm = 0, nr = 0;
-  if (n > 0) {   // (no records: no kernel is launched)
+  if (n > 0 && hex) {
+    r = match_device_hex(s, d_rec, n, &nm, &nr);
+    if (r) return r;
+  } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n);
     if (r) return r;
     MatchParams p{};
@@ -1817,7 +1941,7 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
             (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
   if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
   if (n_matches) *n_matches = nm;
-  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(s->d_mrest);
+  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex ? s->d_hrest : s->d_mrest);
   if (n_rest) *n_rest = nr;
   return YR_AMD_SUCCESS;
 }
@@ -1829,6 +1953,8 @@ int yr_amd_scan_block_matches(yr_amd_scanner* s, const uint8_t* data, size_t siz
   if (s == nullptr || (data == nullptr && size > 0)) return YR_AMD_INVALID_ARGUMENT;
   if (!s->tables->has_strings || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;
   if ((uint64_t)size > YR_AMD_MATCH_MAX_BLOCK) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
+  if ((s->match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
+    return YR_AMD_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(s->tables->device));
   int rg = grow(s->d_block, s->d_block_cap, std::max<size_t>(size, 16));
   if (rg) return rg;
