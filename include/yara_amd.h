@@ -587,10 +587,9 @@ int yr_amd_scan_block_matches(
  * programs (yr_amd_tables_set_re_code; yr_amd_tables_load_yarc attaches them
  * itself) and return YR_AMD_INVALID_ARGUMENT without; more than
  * YR_AMD_MATCH_MAX_RECORDS matches-to-be are refused likewise.  The batch
- * calls (yr_amd_match_batch_device, yr_amd_scan_batch_matches) ignore the
- * setting and stay literal-only: their CSR offsets rely on every buffer
- * keeping its slot range through the sort, which records that expand into
- * several entries do not.
+ * calls (yr_amd_match_batch_device, yr_amd_scan_batch_matches) ignore this
+ * setting: they have one of their own, yr_amd_scanner_set_batch_match_classes
+ * below, and settle literal strings only until that one says otherwise.
  *
  * yr_amd_tables_match_strings: out[k] = 1 iff string k is in one of the
  * classes.  Host code with the preconditions of yr_amd_tables_final_strings,
@@ -807,6 +806,49 @@ int yr_amd_scan_batch_matches(
     const uint64_t** match_off,
     const yr_amd_verify_rec** rest,
     const uint64_t** rest_off);
+
+/*
+ * ---- Final matches of hex strings in a batch (opt-in) ----
+ *
+ * The classes the BATCH match stage settles (yr_amd_match_batch_device,
+ * yr_amd_scan_batch_matches, and so a gathered batch too): YR_AMD_MATCH_LITERAL,
+ * the default, or YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX.  The LITERAL bit must
+ * stay set; YR_AMD_INVALID_ARGUMENT otherwise, for unknown bits and for a NULL
+ * scanner.  The single-block calls never read this setting, and the batch
+ * calls never read yr_amd_scanner_set_match_classes.
+ *
+ * With HEX set, buffer k of a batch gets exactly what
+ * yr_amd_scan_block_matches(data_k, size_k, bases[k]) returns for that buffer
+ * alone on a scanner with yr_amd_scanner_set_match_classes(LITERAL | HEX):
+ *
+ * matches[match_off[k] .. match_off[k + 1]): one entry per distinct (string,
+ * offset) among the matches-to-be of buffer k's records of the classes'
+ * strings -- a record of a final hex string gives one per bytes_matched value
+ * B of its backward program, at offset - B with length B + F -- ascending by
+ * (string, offset), offsets local to the buffer, xor_key 0 for hex; the first
+ * record in record order supplies length and pool_index.  Equal (string,
+ * offset) pairs of different buffers are different matches.
+ * rest[rest_off[k] .. rest_off[k + 1]): buffer k's other records in their
+ * original order, every field unchanged -- among them the records of final hex
+ * strings that the 64-position set cannot measure exactly and those for which
+ * the runs find nothing, as in the single-block stage.
+ *
+ * The buffer is the whole block of both runs: the backward run's
+ * max_bytes_matched is min(local offset, YR_RE_SCAN_LIMIT), the forward run's
+ * min(size_k - local offset, YR_RE_SCAN_LIMIT).  No byte of a gap or of a
+ * neighbouring buffer is read, no match starts before the buffer's byte 0 or
+ * ends past its last byte, and a batch buffer is never a window.
+ * YR_MAX_STRING_MATCHES and the other host state are not applied.
+ *
+ * With HEX set the batch calls need the strings' programs
+ * (yr_amd_tables_set_re_code) and return YR_AMD_INVALID_ARGUMENT without --
+ * yr_amd_scan_batch_matches before any copy -- and refuse more than
+ * YR_AMD_MATCH_MAX_RECORDS matches-to-be likewise; every other refusal of the
+ * batch calls stays.  yr_amd_match_batch_device then waits twice (the count of
+ * matches-to-be sizes the sort).  With the default the batch stage launches
+ * what it launches without this setting.
+ */
+int yr_amd_scanner_set_batch_match_classes(yr_amd_scanner* scanner, uint32_t classes);
 
 /*
  * ---- Block pipeline ----

@@ -31,8 +31,9 @@ block path above.
 or jumps that are no chain parts), measured on the GPU as yr_re_fast_exec does;
 a call of one can be several matches.  The calls left are then those of
 regexps, chain parts and base64 strings (and hex calls whose jumps span more
-than 64 positions).  The batch calls are literal-only, so with --hex every file
-takes the block path.
+than 64 positions).  Several files go through batches as without --hex
+(yr_amd_scanner_set_batch_match_classes): only the files above BLOCK bytes take
+the block path.
 """
 import gzip
 import os
@@ -94,6 +95,7 @@ def main():
     sc = yara_amd.Scanner(tables)
     if hex_class:
         sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+        sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
     paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))
@@ -103,7 +105,7 @@ def main():
         return
     sizes = [os.path.getsize(p) for p in paths]
     per, left = [None] * len(paths), 0
-    for group in ([] if hex_class else arenas(sizes)):
+    for group in arenas(sizes):
         try:
             m, mo, rest, _ = sc.batch_string_matches(
                 [np.fromfile(paths[k], dtype=np.uint8) for k in group])
@@ -115,7 +117,7 @@ def main():
             per[k] = m[int(mo[j]):int(mo[j + 1])]
         left += len(rest)
     for k, p in enumerate(paths):
-        if per[k] is None:   # larger than BLOCK, or --hex
+        if per[k] is None:   # larger than BLOCK
             per[k], n = block_path(sc, np.fromfile(p, dtype=np.uint8))
             left += n
         for r in per[k]:

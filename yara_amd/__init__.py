@@ -269,6 +269,7 @@ class Scanner:
         self.tables = tables
         self._batch_n = 0   # buffers of the last scan_batch_device
         self._classes = MATCH_LITERAL   # set_match_classes
+        self._batch_classes = MATCH_LITERAL   # set_batch_match_classes
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -337,7 +338,8 @@ class Scanner:
     def set_match_classes(self, classes: int):
         """The string classes the match stage settles
         (yr_amd_scanner_set_match_classes): MATCH_LITERAL (the default), or
-        MATCH_LITERAL | MATCH_HEX.  The batch calls stay literal-only."""
+        MATCH_LITERAL | MATCH_HEX.  The batch calls ignore it: they have
+        set_batch_match_classes."""
         _lib.check("yr_amd_scanner_set_match_classes",
                    _lib.lib().yr_amd_scanner_set_match_classes(self._h, classes))
         self._classes = classes
@@ -352,6 +354,25 @@ class Scanner:
             return call()
         finally:
             self.set_match_classes(was)
+
+    def set_batch_match_classes(self, classes: int):
+        """The string classes the BATCH match stage settles
+        (yr_amd_scanner_set_batch_match_classes): MATCH_LITERAL (the default),
+        or MATCH_LITERAL | MATCH_HEX.  The single-block calls ignore it."""
+        _lib.check("yr_amd_scanner_set_batch_match_classes",
+                   _lib.lib().yr_amd_scanner_set_batch_match_classes(self._h, classes))
+        self._batch_classes = classes
+
+    def _with_batch_hex(self, hex, call):
+        # _with_hex for the batch calls' setting
+        was = self._batch_classes
+        if not hex or (was & MATCH_HEX):
+            return call()
+        self.set_batch_match_classes(was | MATCH_HEX)
+        try:
+            return call()
+        finally:
+            self.set_batch_match_classes(was)
 
     def match_device(self, data_base: int = 0, hex: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
@@ -539,12 +560,19 @@ class Scanner:
         return self.verify_batch_device(bases)
 
     # -- final matches of a batch ------------------------------------------------
-    def match_batch_device(self, bases=None):
+    def match_batch_device(self, bases=None, hex: bool = False):
         """(matches, match_off, rest, rest_off) of the last completed batch scan
         (yr_amd_match_batch_device), copied to the host: buffer k's
         ``matches[match_off[k]:match_off[k + 1]]`` and
         ``rest[rest_off[k]:rest_off[k + 1]]`` are what ``string_matches`` gives
-        for that buffer alone (offsets local to the buffer)."""
+        for that buffer alone (offsets local to the buffer).  ``hex=True``
+        settles the final hex strings too for this call, as
+        ``string_matches(hex=True)`` does for the buffer alone; ``hex=False``
+        leaves the scanner's batch classes (set_batch_match_classes) as they
+        are."""
+        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases))
+
+    def _match_batch_device(self, bases):
         from ._hip import memcpy
         b = None if bases is None else _arr(bases, np.uint64).reshape(-1)
         if b is not None and b.size != self._batch_n:
@@ -564,11 +592,14 @@ class Scanner:
             memcpy(rest.ctypes.data, pr.value, rest.size * 16, 2)
         return matches, match_off, rest, rest_off
 
-    def batch_string_matches(self, buffers, bases=None):
+    def batch_string_matches(self, buffers, bases=None, hex: bool = False):
         """(matches, match_off, rest, rest_off) of a list of host buffers
         (yr_amd_scan_batch_matches): buffer k's slices equal
-        ``string_matches(buffers[k], bases[k])``.  One scan, one
+        ``string_matches(buffers[k], bases[k], hex=hex)``.  One scan, one
         pre-verification and one match stage for all of them."""
+        return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases))
+
+    def _batch_string_matches(self, buffers, bases):
         bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
         n = len(bufs)
         ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
@@ -593,7 +624,7 @@ class Scanner:
             ctypes.memmove(rest.ctypes.data, pr, rest.size * 16)
         return matches, match_off, rest, rest_off
 
-    def batch_string_matches_device(self, buffers, bases=None):
+    def batch_string_matches_device(self, buffers, bases=None, hex: bool = False):
         """batch_string_matches for buffers in device memory (see
         batch_candidates_device), through the gather call."""
         ptrs, sizes = _device_buffers(buffers)
@@ -601,7 +632,7 @@ class Scanner:
             raise ValueError("one base per buffer")
         self.scan_batch_gather_device(ptrs, sizes)
         self.batch_result()
-        return self.match_batch_device(bases)
+        return self.match_batch_device(bases, hex=hex)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

@@ -167,6 +167,7 @@ PROTOTYPES = {
     "yr_amd_tables_device": (_int, [_vp]),
     "yr_amd_tables_set_profiling": (_int, [_vp, _int]),
     "yr_amd_scanner_set_match_classes": (_int, [_vp, ctypes.c_uint32]),
+    "yr_amd_scanner_set_batch_match_classes": (_int, [_vp, ctypes.c_uint32]),
     "yr_amd_tables_match_strings": (_int, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
 }
 

@@ -172,4 +172,39 @@ hipError_t launch_hex_expand(const HexMatchParams& p, hipStream_t s);
 // length plus the distance from the item's offset to the record's.
 hipError_t launch_hex_unique(const HexMatchParams& p, int pass, hipStream_t s);
 
+// ---- The batch's stage with the hex class (yr_amd_scanner_set_batch_match_classes) ----
+// Both of the above at once: records become items as in HexMatchParams, and
+// the CSR of the matches is counted over ITEMS.  hex_expand_kernel writes the
+// items ascending by record, i.e. by buffer, so buffer k's items hold the slots
+// [item_off[k], item_off[k + 1]) -- item_off[k] = the items of the records
+// below rec_off[k] -- and the sort by (buffer, string, offset) keeps them
+// there, as it keeps the records' slots in BatchMatchParams.  An item's value
+// is its record, and buf[] is by record: buf[index[i]] is the item's buffer
+// (the buffer passes of batch_match_sort as they are).
+// A struct of its own: HexMatchParams and BatchMatchParams are kernel
+// arguments of the kernels above, which stay what they are.  The rest goes
+// through match_rest_kernel and batch_match_offsets_kernel<0> (h.m.keys /
+// h.m.block_off / h.m.chunk_off are per record, as in HexMatchParams), the
+// expansion through hex_expand_kernel.
+struct BatchHexParams {
+  HexMatchParams h;             // h.m.data = the arena; size, win_lo, win_hi unused
+  const uint64_t* starts;       // [nbuf] the buffers in the arena
+  const uint64_t* sizes;        // [nbuf]
+  const uint64_t* rec_off;      // [nbuf + 1] CSR of h.m.recs
+  uint32_t nbuf;
+  uint32_t* buf;                // [h.m.n] by record: its buffer
+  uint64_t* item_off;           // [nbuf + 1] CSR of the items
+  uint64_t* match_off;          // [nbuf + 1] CSR of h.m.out
+};
+
+// Measure: as launch_hex_measure, each record in its own buffer, + buf.
+hipError_t launch_batch_hex_measure(const BatchHexParams& p, hipStream_t s);
+// matches == 0: item_off from the scanned item counts (iblock_off / ichunk_off);
+// 1: match_off from the scanned unique counts (after launch_batch_hex_unique 0)
+// at the slots item_off names.
+hipError_t launch_batch_hex_offsets(const BatchHexParams& p, int matches, hipStream_t s);
+// As launch_hex_unique; an item is kept iff it is a match and its key or its
+// record's buffer differs from its predecessor's.
+hipError_t launch_batch_hex_unique(const BatchHexParams& p, int pass, hipStream_t s);
+
 }  // namespace yamd

@@ -30,6 +30,8 @@
 // hex string is measured too and can be several matches: hex_measure_kernel,
 // hex_expand_kernel and hex_unique_kernel below take the place of 1. and 3.,
 // the sort runs over the items (matches.h HexMatchParams).
+// A batch with the hex class (yr_amd_scanner_set_batch_match_classes) counts
+// its CSR over the items: the batch_hex_* kernels (BatchHexParams, 18.3).
 //
 // The comparisons are restated here rather than shared with verify.hip: that
 // file's kernels stay byte for byte what they were (their register budgets are
@@ -675,6 +677,120 @@ __global__ __launch_bounds__(256) void hex_unique_kernel(HexMatchParams q) {
   p.out[q.uchunk_off[g / kChunkGroups] + q.ublock_off[g] + lanes_below(mask)] = o;
 }
 
+// ---- The batch's stage with the hex class (matches.h BatchHexParams) ----
+// hex_measure_kernel with batch_match_classify_kernel's view: the record's
+// buffer is the whole block of both runs (max_bytes_matched = min(local
+// offset, YR_RE_SCAN_LIMIT) backwards, min(size - local offset, ...) forwards),
+// never a window -- hex_run reads live positions only, so no byte of a gap or
+// of a neighbouring buffer.
+__global__ __launch_bounds__(256) void batch_hex_measure_kernel(BatchHexParams b) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const MatchParams& p = b.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool rest = false;
+  uint32_t items = 0;
+  if (r < p.n) {
+    uint32_t lo = 0, hi = b.nbuf;   // rec_off[lo] <= r < rec_off[hi]  (rec_off[nbuf] == n)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (b.rec_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    HexMatchParams q = b.h;
+    q.m.data = p.data + b.starts[lo];
+    q.m.size = b.sizes[lo];
+    q.m.win_lo = 0;
+    q.m.win_hi = q.m.size;
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      is_match = measure_hex(q, e, rec.offset, buf, m, set) == kHexMatch;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(q.m, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? p.pool_string[rec.pool_index] : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    b.h.sets[r] = set;
+    b.buf[r] = lo;
+    rest = !is_match;
+    items = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  const uint64_t mask = __ballot(rest);
+  const uint32_t total = (uint32_t)__shfl((int)wave_prefix(items), 63, 64);
+  if ((threadIdx.x & 63u) == 0 && r < p.n) {
+    p.block_off[r / kGroup] = (uint64_t)__popcll(mask);
+    b.h.iblock_off[r / kGroup] = (uint64_t)total;
+  }
+}
+
+// Item i of the sorted arrays opens a run of one (buffer, string, offset).
+__device__ __forceinline__ bool batch_hex_keep(const BatchHexParams& b, uint64_t i, uint64_t key) {
+  const MatchParams& p = b.h.m;
+  if ((uint32_t)(key >> 32) >= p.n_strings) return false;
+  return i == 0 || p.sorted_keys[i - 1] != key ||
+         b.buf[p.sorted_index[i - 1]] != b.buf[p.sorted_index[i]];
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void batch_hex_unique_kernel(BatchHexParams b) {
+  const MatchParams& p = b.h.m;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  uint64_t key = 0;
+  if (i < b.h.n_items) {
+    key = p.sorted_keys[i];
+    keep = batch_hex_keep(b, i, key);
+  }
+  const uint64_t mask = __ballot(keep);
+  if (PASS == 0) {
+    if ((threadIdx.x & 63u) == 0 && i < b.h.n_items)
+      b.h.ublock_off[i / kGroup] = (uint64_t)__popcll(mask);
+    return;
+  }
+  if (!keep) return;
+  const uint32_t r = p.sorted_index[i];   // the buffer's first record with this (string, offset)
+  const MatchMeasure m = p.meas[r];
+  const VerifyRec rec = p.recs[r];
+  MatchRec o;
+  o.offset = key & 0xFFFFFFFFull;
+  o.string = (uint32_t)(key >> 32);
+  o.length = m.length + (uint32_t)((rec.offset & 0xFFFFFFFFull) - o.offset);   // B + F
+  o.xor_key = m.xor_key;
+  o.pool_index = rec.pool_index;
+  const uint64_t g = i / kGroup;
+  p.out[b.h.uchunk_off[g / kChunkGroups] + b.h.ublock_off[g] + lanes_below(mask)] = o;
+}
+
+// The CSR offsets over items, one lane per k in [0, nbuf] (as
+// batch_match_offsets_kernel counts over records).  MATCHES 0: item_off[k] =
+// the items of the records below c0 = rec_off[k]: the scanned item count of
+// c0's wave plus the item counts of the wave's records below c0.  1:
+// match_off[k] = the kept entries below slot c0 = item_off[k] of the sorted
+// arrays.  (g == groups: the entry past the last wave, the total.)
+template <int MATCHES>
+__global__ __launch_bounds__(256) void batch_hex_offsets_kernel(BatchHexParams b) {
+  const MatchParams& p = b.h.m;
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > b.nbuf) return;
+  const uint64_t c0 = MATCHES ? b.item_off[k] : b.rec_off[k], g = c0 / kGroup;
+  uint64_t o = MATCHES ? b.h.uchunk_off[g / kChunkGroups] + b.h.ublock_off[g]
+                       : b.h.ichunk_off[g / kChunkGroups] + b.h.iblock_off[g];
+  for (uint64_t c = g * kGroup; c < c0; ++c) {
+    if (MATCHES)
+      o += batch_hex_keep(b, c, p.sorted_keys[c]) ? 1u : 0u;
+    else
+      o += hex_items(p.keys[c], p.n_strings, b.h.sets[c]);
+  }
+  (MATCHES ? b.match_off : b.item_off)[k] = o;
+}
+
 }  // namespace
 
 hipError_t launch_match_classify(const MatchParams& p, hipStream_t s) {
@@ -813,6 +929,36 @@ hipError_t launch_batch_match_unique(const BatchMatchParams& p, int pass, hipStr
     hipLaunchKernelGGL(batch_match_unique_kernel<0>, match_grid(p.m.n), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(batch_match_unique_kernel<1>, match_grid(p.m.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_hex_measure(const BatchHexParams& p, hipStream_t s) {
+  if (p.h.m.n == 0 || p.h.m.n > kMatchMaxRecords || p.nbuf == 0)
+    return p.h.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_hex_measure_kernel, match_grid(p.h.m.n), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_hex_offsets(const BatchHexParams& p, int matches, hipStream_t s) {
+  if (p.h.m.n == 0 || p.h.m.n > kMatchMaxRecords)
+    return p.h.m.n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (matches && (p.h.n_items == 0 || p.h.n_items > kMatchMaxRecords))
+    return p.h.n_items == 0 ? hipSuccess : hipErrorInvalidValue;
+  const dim3 grid = match_grid((uint64_t)p.nbuf + 1);
+  if (matches)
+    hipLaunchKernelGGL(batch_hex_offsets_kernel<1>, grid, dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(batch_hex_offsets_kernel<0>, grid, dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_hex_unique(const BatchHexParams& p, int pass, hipStream_t s) {
+  if (p.h.n_items == 0 || p.h.n_items > kMatchMaxRecords)
+    return p.h.n_items == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (pass == 0)
+    hipLaunchKernelGGL(batch_hex_unique_kernel<0>, match_grid(p.h.n_items), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(batch_hex_unique_kernel<1>, match_grid(p.h.n_items), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

@@ -233,12 +233,15 @@ struct yr_amd_scanner {
   // the batch's match stage (yr_amd_match_batch_device; matches.h BatchMatchParams)
   uint32_t* d_mbuf = nullptr;           // [cap] each record's buffer
   size_t mbuf_cap = 0;
-  uint64_t* d_moff = nullptr;           // [2 * (n + 1)]: match_off, rest_off
+  uint64_t* d_moff = nullptr;           // [2 * (n + 1)]: match_off, rest_off (hex: + item_off)
   size_t moff_cap = 0;
   std::vector<uint64_t> h_match_off, h_mrest_off;
   // the stage with the hex class (yr_amd_scanner_set_match_classes; matches.h
   // HexMatchParams): the arrays by RECORD -- the workspace above then holds items
   uint32_t match_classes = kMatchLiteral;
+  // the batch's classes (yr_amd_scanner_set_batch_match_classes; matches.h
+  // BatchHexParams): with hex, d_moff holds a third array, item_off
+  uint32_t batch_match_classes = kMatchLiteral;
   uint64_t* d_hkeys = nullptr;          // [cap] the records' keys
   size_t hkeys_cap = 0;
   MatchMeasure* d_hmeas = nullptr;      // [cap]
@@ -2319,6 +2322,130 @@ int yr_amd_scan_batch_gather_device(yr_amd_scanner* s, const uint8_t* const* d_b
 
 // ---- Final matches of a batch (matches.hip BatchMatchParams) ----
 
+extern "C++" {
+namespace {
+// The batch's stage with the hex class: records -> items -> matches, the CSR
+// of the matches counted over the items (matches.h BatchHexParams).  Two
+// waits, as match_device_hex: the item count sizes the sort's workspace.  The
+// offsets go to s->h_mrest_off (first wait) and s->h_match_off (second; zeros
+// without items).
+int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n,
+                           uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni) {
+  const yr_amd_tables* t = s->tables;
+  const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
+  const size_t noff = (size_t)nbuf + 1;
+  int r = ensure_match_workspace(s, 1);   // (the pinned totals; the items' arrays grow below)
+  if (!r) r = grow_geo(s->d_hkeys, s->hkeys_cap, n);
+  if (!r) r = grow_geo(s->d_hmeas, s->hmeas_cap, n);
+  if (!r) r = grow_geo(s->d_hsets, s->hsets_cap, n);
+  if (!r) r = grow_geo(s->d_hrest, s->hrest_cap, n);
+  if (!r) r = grow_geo(s->d_hblock, s->hblock_cap, 2 * groups);
+  if (!r) r = grow_geo(s->d_hchunk, s->hchunk_cap, 2 * chunks);
+  if (!r) r = grow_geo(s->d_mbuf, s->mbuf_cap, n);
+  if (!r) r = grow_geo(s->d_moff, s->moff_cap, 3 * noff);   // match_off, rest_off, item_off
+  if (r) return r;
+  BatchHexParams b{};
+  MatchParams& m = b.h.m;
+  m.data = s->last.data;
+  m.recs = reinterpret_cast<const VerifyRec*>(d_rec);
+  m.n = n;
+  m.pool = t->d_pool;
+  m.pool_string = t->d_pool_string;
+  m.n_strings = (uint32_t)t->h_str_flags.size();
+  m.str_bytes = t->d_str_bytes;
+  m.lowercase = t->d_lowercase;
+  m.keys = s->d_hkeys;
+  m.meas = s->d_hmeas;
+  m.block_off = s->d_hblock;
+  m.chunk_off = s->d_hchunk;
+  m.rest = s->d_hrest;
+  b.h.re_code = t->d_re_code;
+  b.h.classes = s->batch_match_classes;
+  b.h.sets = s->d_hsets;
+  b.h.iblock_off = s->d_hblock + groups;
+  b.h.ichunk_off = s->d_hchunk + chunks;
+  b.starts = s->d_bstarts;
+  b.sizes = s->d_bstarts + nbuf;
+  b.rec_off = s->d_boff + noff;   // (built by yr_amd_verify_batch_device)
+  b.nbuf = nbuf;
+  b.buf = s->d_mbuf;
+  b.match_off = s->d_moff;
+  b.item_off = s->d_moff + 2 * noff;
+  // the rest's CSR is the literal batch's: the same kernel over the records' keys
+  BatchMatchParams rp{};
+  rp.m = m;
+  rp.rec_off = b.rec_off;
+  rp.nbuf = nbuf;
+  rp.rest_off = s->d_moff + noff;
+  const KeptLists none{{0, 0, 0, 0}};
+  // measure -> the offsets of the rest and of the items -> the rest, its CSR
+  // and the items' CSR; wait
+  HIP_TRY(launch_batch_hex_measure(b, s->stream));
+  HIP_TRY(launch_block_offsets(m.block_off, m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
+  HIP_TRY(launch_block_offsets(b.h.iblock_off, b.h.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
+                               s->stream));
+  HIP_TRY(launch_match_rest(m, s->stream));
+  HIP_TRY(launch_batch_match_offsets(rp, 0, s->stream));
+  HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_mrest_off.data(), rp.rest_off, noff * sizeof(uint64_t),
+                         hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *nr = s->h_msum[0];
+  const uint64_t items = s->h_msum[3];
+  *ni = items;
+  *nm = 0;
+  if (*nr > n || items > 64 * (n - *nr) || s->h_mrest_off[nbuf] != *nr)
+    return YR_AMD_INTERNAL_FATAL_ERROR;
+  if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
+  if (items == 0) return YR_AMD_SUCCESS;
+  r = ensure_match_workspace(s, items);
+  if (r) return r;
+  b.h.n_items = items;
+  b.h.ikeys = s->d_mkeys;
+  b.h.iindex = s->d_mindex;
+  b.h.ublock_off = s->d_mblock;
+  b.h.uchunk_off = s->d_mchunk;
+  m.out = s->d_mout;
+  // the key's bits that vary: the local offsets' (below the largest buffer's
+  // size; offset - B only decreases), and the string field's
+  uint64_t largest = 1;
+  for (uint64_t z : s->h_bsizes) largest = std::max(largest, z);
+  int lo_bits = 1, hi_bits = 1;
+  while (lo_bits < 32 && ((largest - 1) >> lo_bits) != 0) ++lo_bits;
+  while (hi_bits < 32 && (m.n_strings >> hi_bits) != 0) ++hi_bits;
+  uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+  uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+  // expand; sort by (buffer, string, offset); distinct (buffer, key) -> their
+  // offsets -> the matches and their CSR; wait
+  HIP_TRY(launch_hex_expand(b.h, s->stream));
+  int sorted = 0;
+  HIP_TRY(batch_match_sort(keys, index, items, lo_bits, hi_bits, b.buf, nbuf, s->d_mhist,
+                           s->d_mhchunk, s->d_mhsum + 2, s->stream, &sorted));
+  m.sorted_keys = keys[sorted];
+  m.sorted_index = index[sorted];
+  HIP_TRY(launch_batch_hex_unique(b, 0, s->stream));
+  HIP_TRY(launch_block_offsets(b.h.ublock_off, b.h.uchunk_off, items, s->d_mhsum + 1, nullptr, none,
+                               s->stream));
+  HIP_TRY(launch_batch_hex_unique(b, 1, s->stream));
+  HIP_TRY(launch_batch_hex_offsets(b, 1, s->stream));
+  HIP_TRY(hipMemcpyAsync(s->h_match_off.data(), b.match_off, noff * sizeof(uint64_t),
+                         hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *nm = s->h_msum[1];
+  if (*nm > items || s->h_match_off[nbuf] != *nm) return YR_AMD_INTERNAL_FATAL_ERROR;
+  return YR_AMD_SUCCESS;
+}
+}  // namespace
+}  // extern "C++"
+
+int yr_amd_scanner_set_batch_match_classes(yr_amd_scanner* s, uint32_t classes) {
+  if (s == nullptr || !(classes & YR_AMD_MATCH_LITERAL) ||
+      (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
+    return YR_AMD_INVALID_ARGUMENT;
+  s->batch_match_classes = classes;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
                               const yr_amd_match_rec** d_matches, const uint64_t** match_off,
                               const yr_amd_verify_rec** d_rest, const uint64_t** rest_off) {
@@ -2326,6 +2453,9 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   // (count-only records are no calls: they have no match meaning)
   if (s->tables->profile) return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_tables* t = s->tables;
+  // the hex class interprets the strings' programs (yr_amd_tables_set_re_code)
+  const bool hex = (s->batch_match_classes & kMatchHex) != 0;
+  if (hex && t->d_re_code == nullptr) return YR_AMD_INVALID_ARGUMENT;
   const yr_amd_verify_rec* d_rec = nullptr;
   const uint64_t* rec_off = nullptr;
   int r = yr_amd_verify_batch_device(s, bases, &d_rec, &rec_off);
@@ -2335,8 +2465,11 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   s->h_match_off.assign((size_t)nbuf + 1, 0);
   s->h_mrest_off.assign((size_t)nbuf + 1, 0);
-  uint64_t nm = 0, nr = 0;
-  if (n > 0) {   // (no records: no kernel is launched)
+  uint64_t nm = 0, nr = 0, ni = 0;
+  if (n > 0 && hex) {
+    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni);
+    if (r) return r;
+  } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n, nbuf);
     if (r) return r;
     BatchMatchParams p{};
@@ -2399,14 +2532,20 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
     if (nr > n || nm > n - nr || s->h_match_off[nbuf] != nm || s->h_mrest_off[nbuf] != nr)
       return YR_AMD_INTERNAL_FATAL_ERROR;
   }
-  if (debug_level() >= 1)
+  if (debug_level() >= 1 && hex)
+    fprintf(stderr,
+            "- %u buffers, %llu verify calls -> %llu items -> %llu matches, %llu calls left // "
+            "yr_amd_match_batch_device()\n",
+            nbuf, (unsigned long long)n, (unsigned long long)ni, (unsigned long long)nm,
+            (unsigned long long)nr);
+  else if (debug_level() >= 1)
     fprintf(stderr,
             "- %u buffers, %llu verify calls -> %llu matches, %llu calls left // "
             "yr_amd_match_batch_device()\n",
             nbuf, (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
   if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
   if (match_off) *match_off = s->h_match_off.data();
-  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(s->d_mrest);
+  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex ? s->d_hrest : s->d_mrest);
   if (rest_off) *rest_off = s->h_mrest_off.data();
   return YR_AMD_SUCCESS;
 }
@@ -2416,6 +2555,8 @@ int yr_amd_scan_batch_matches(yr_amd_scanner* s, const uint8_t* const* data, con
                               const uint64_t** match_off, const yr_amd_verify_rec** rest,
                               const uint64_t** rest_off) {
   if (s == nullptr || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
+  if ((s->batch_match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
+    return YR_AMD_INVALID_ARGUMENT;
   int r = scan_batch_host(s, data, sizes, n);
   const yr_amd_match_rec* d_m = nullptr;
   const yr_amd_verify_rec* d_r = nullptr;
