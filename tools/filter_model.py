@@ -33,6 +33,13 @@ stream 0.637, stage 1 0.666, + appends 0.771, product 0.839):
   sets' kernels): VALU per tile = stage-1 VALU + 12 x tiles appending + 5 x
   filter-pass entries, 7 us each, relative to the product's 122.5.
 
+Dual-role rates (the drain's other-role probe, kernels.hip other_role_pass):
+every key window sits in the product's filter in both roles, so a position
+that passes the role its parity gives it can be probed again in the other
+one; "dual_role" in the output has the rate of each role alone, of both, and
+of the inherent key windows (config C, 64 MiB: 0.392 %, 0.393 %, 0.089 %,
+0.069 %).
+
     python tools/filter_model.py [--mib 64] > profiles/r05_filter_model.json
 """
 import argparse
@@ -168,6 +175,25 @@ STAGE1 = {
 DRAIN_SHARE = {"pair_mask": 100.0 / 233.0}         # the re-test (133 of ~233 slots per drain) skipped
 
 
+def dual_role_rates(z, mib):
+    """Pass rates of the product's pair filter on `mib` MiB of the bench's
+    seed-1 input: the role a position's parity gives it, the other role, both,
+    and the windows that are key windows (z: a tests/golden/tables npz without
+    1- or 2-byte keys)."""
+    import oracle
+    W = windows3(keys_of(z["T"], z["M"]))
+    f = build("pair", W)
+    data = oracle.xorshift(mib << 20, 1).astype(np.int64)
+    w = data[:-2] | (data[1:-1] << 8) | (data[2:] << 16)
+    par = np.arange(2, data.size) & 1
+    own = np.where(par == 0, test("pair", f, w, 0), test("pair", f, w, 1))
+    other = np.where(par == 0, test("pair", f, w, 1), test("pair", f, w, 0))
+    key3 = np.isin(w, np.array(W))
+    assert (own[key3] == 1).all() and (other[key3] == 1).all()   # neither role loses a key window
+    return {"own_role_pass": float(own.mean()), "other_role_pass": float(other.mean()),
+            "both_roles_pass": float((own & other).mean()), "inherent_window_rate": float(key3.mean())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mib", type=int, default=64)
@@ -184,6 +210,7 @@ def main():
     key3 = np.isin(w, np.array(W))         # inherent: the window is a key window
     out = {"what": __doc__.split("\n\n")[0], "keys_by_length": {k: len(v) for k, v in keys.items()},
            "key_windows": len(W), "sample_mib": a.mib, "inherent_window_rate": float(key3.mean()),
+           "dual_role": {k: round(v, 5) for k, v in dual_role_rates(z, a.mib).items()},
            "designs": {}}
     base = None
     for d in ("pair", "pair_xor", "single", "pair_k3", "pair_1bit", "pair_mask", "pair_1w"):

@@ -18,11 +18,12 @@
 //             The main loop only asks "does some position of the lane pass".
 //   stage 2 (filter hits):  lanes that pass append their 20 bytes of window
 //             context, in position order, to a per-wave LDS ring; a drain
-//             (one entry per lane) re-tests the 16 positions, sends each hit
-//             through a first-level word filter (L2) and the survivors
-//             through bucketed two-choice tables (L2); exact hits are
-//             compacted in order (ballot + mbcnt / DPP prefix sums) into the
-//             segment's output.
+//             (one entry per lane) re-tests the 16 positions and probes each
+//             hit in the filter's other role (LDS; the even-filter kernels:
+//             the first-level word filter instead); the survivors go, 64 at
+//             a time, through a first-level word filter (L2) and bucketed
+//             two-choice tables (L2); exact hits are compacted in order
+//             (ballot + mbcnt / DPP prefix sums) into the segment's output.
 //
 // Memory: the input is streamed once, 16 B per lane (1 KiB per wave per step,
 // buffer loads), tiles t+1 and t+2 in flight while tile t is filtered
@@ -149,6 +150,30 @@ __device__ __forceinline__ uint32_t window4(uint32_t ent, uint32_t j) {
   return *reinterpret_cast<const __attribute__((address_space(3))) u32_una*>((uintptr_t)(ent + kEntData + j - 3));
 }
 
+// The pair filter again, in the role the position's parity does NOT give it.
+// tables.cpp puts every key window into the filter in both roles
+// (filter_probe_left and filter_probe_right: another block, other bit
+// fields), so a key window passes this probe too, and a random window that
+// passed its own role passes it about one time in four (config C: 0.39 % of
+// positions pass one role, 0.089 % both; tools/filter_model.py dual_role).
+// Stage 1 and the drain's re-test give even lane bytes the left role and odd
+// ones the right role (stage1: position 2j left, 2j + 1 right), so lane byte
+// j is probed right if even, left if odd.  w4 = window4 of the position: the
+// window is its upper three bytes.  One ds_read_b64, no table access.
+__device__ __forceinline__ bool other_role_pass(uint32_t w4, uint32_t j) {
+  // Both roles from one bit string, without a branch on the parity: X = the
+  // window x followed by itself, X[24 + i] = x[i] (its low dword: window
+  // bytes 0, 1, 2, 0; the next one: x >> 8).  Left: block x[10..23], bits
+  // x[0..4] / x[5..9] = X >> 10, X >> 0, X >> 5.  Right: block x[2..15], bits
+  // x[16..20] / x[21..23] x[0..1] = X >> 26, X >> 16, X >> 21: the same three
+  // fields 16 bits further up.  (The shifters read 5 bits of the amount.)
+  const uint32_t X = __builtin_amdgcn_perm(w4, w4, 0x01030201u);
+  const uint32_t s = (~j & 1u) << 4;   // even lane byte: the right role
+  const uint32_t addr = __builtin_amdgcn_alignbit(w4 >> 16, X, s + 7u) & (kFilterBytes - 8);
+  const u32x2 w = lds_load<u32x2>(addr);
+  return ((w.x >> ((X >> s) & 31u)) & (w.y >> ((X >> (s + 5u)) & 31u)) & 1u) != 0u;
+}
+
 // Lane byte (0..15) of bit b of a tile hit mask: bit 8n + r <=> byte 4n + r.
 __device__ __forceinline__ uint32_t mask_position(uint32_t b) { return ((b >> 3) << 2) | (b & 3u); }
 
@@ -251,13 +276,17 @@ __device__ __forceinline__ void right_shifts(uint32_t y2, uint32_t j, uint32_t w
 // filter per position from the context, and needs no global load of the
 // input, only table probes.
 //
-// Drains run the first level of the exact check (internal.h fl_word: one
-// dword per hit) over 64 entries; the few hits that pass it go, in order, to
-// a per-wave pending list of (window, offset) pairs, and the bucket probes
-// run once that list holds a wave's worth -- one lane per hit, one round
-// trip per 64 hits instead of one per drain.  (Rounds 1-5 deferred the
-// first-level loads to the next tile step; with more than one tile in flight
-// that costs more than it hides -- DESIGN.md section 5.2.)
+// The pair-filter kernel's drains (tables without 1- or 2-byte keys) probe
+// each hit in the filter's other role (other_role_pass: LDS only); the one in
+// four that passes goes, in order, to a per-wave pending list of (window,
+// offset) pairs.  Once that list holds a wave's worth, flush_pending runs the
+// first level of the exact check (internal.h fl_word: one dword per hit) and
+// the bucket probes -- one lane per hit, one or two round trips per 64 hits
+// and none per drain (C -1.7 %).  The even-filter
+// kernels hold one role only: their drains run the first level themselves,
+// one dependent load per hit, and pend its survivors.  (Rounds 1-5 deferred
+// those loads to the next tile step; with more than one tile in flight that
+// costs more than it hides -- section 5.2.)
 struct WaveQueue {
   uint32_t ring;    // LDS address: kQueueCap entries of kQueueEntryWords dwords
   uint32_t count;   // wave-uniform: entries in the ring (a drain takes all of them)
@@ -349,6 +378,13 @@ constexpr int kStage1Mode = !(kByteKeys<MODE> || MODE == 24 || MODE == 25) ? kBa
 // not even detected.  Both on a 1-byte-key rule set; output wrong by construction.
 template <int MODE>
 constexpr bool kByteKeyAblation = MODE == 24 || MODE == 25;
+// The pair-filter product kernel (and its ablations that keep the drains'
+// meaning) on tables without 1- or 2-byte keys: the drain probes each hit in
+// the filter's other role (other_role_pass) and makes no global load; the
+// first level runs in flush_pending.  The even-filter kernels hold the left
+// role only and keep the first level in the drain.
+template <int MODE>
+constexpr bool kOtherRole = MODE == 0 || MODE == 11 || MODE == 12;
 // The ring entry's index word holds the lane's byte offset in the segment
 // (else its 16-byte unit index, with the next lane's first two bytes on top)
 template <int MODE>
@@ -475,8 +511,9 @@ __device__ __forceinline__ KeyClassRec scan_key_rec(uint32_t kcv, uint32_t k, bo
   return r;
 }
 
-// Bucket-probe every pending hit (one lane each) and append the survivors,
-// in order, to the segment's output.  Verified-only scans (p.drop_dead):
+// Bucket-probe every pending hit (one lane each; kOtherRole: behind the first
+// level) and append the survivors, in order, to the segment's output.
+// Verified-only scans (p.drop_dead):
 // certain candidates of class dead are left out but still counted in the
 // segment's full stream (q.full), and seg_x gets each output candidate's
 // index in that stream.
@@ -502,10 +539,20 @@ __device__ __forceinline__ void flush_pending(const ScanParams& p, WaveQueue& q,
     if (__ballot(probe) != 0 && probe) keep = exact_check(e.x, seg_start + off + 1, p);
     xv = e.x;
     dx = conf ? e.x : (e.y >> kOutByteShift) & 0xFFu;   // (kDrop: the dead its drain dropped before it)
+  } else if constexpr (kOtherRole<MODE>) {
+    // the first level here, one lane per hit; the bucket loads behind a
+    // wave-uniform test, so a flush whose hits all fail it makes one round
+    // trip.  (Tables with 1- or 2-byte keys: first_level is true, no load.)
+    u32x2 e = {0u, 0u};
+    if (lane < q.pend_n) e = lds_load<u32x2>(q.pend + 8 * lane);
+    off = e.y;
+    keep = lane < q.pend_n && first_level(e.x, p);
+    if (MODE != 12 && __ballot(keep) != 0 && keep)   // 12: ablation, no buckets
+      keep = exact_check(e.x, seg_start + off + 1, p);
   } else if (lane < q.pend_n) {
     const u32x2 e = lds_load<u32x2>(q.pend + 8 * lane);
     off = e.y;
-    keep = MODE == 12 ? true : exact_check(e.x, seg_start + off + 1, p);   // 12: ablation
+    keep = exact_check(e.x, seg_start + off + 1, p);
   }
   const uint64_t b = __ballot(keep);
   uint64_t bf = b;   // the segment's full stream: kept and dead candidates
@@ -701,8 +748,9 @@ __device__ __forceinline__ uint32_t byte_keys_mask(const uint32_t (&S)[6], const
 #define YAMD_EXPECT(c, v) __builtin_expect((c), (v))
 // Tiles in flight ahead of the one in the tile step (scan_segment).  Two
 // instead of one: C -4 %, rx -8 %, E -2 % (profiles/r06_prefetch_ab/) --
-// once the drains check the first level themselves instead of deferring its
-// loads to the next tile step (rounds 1-5): vmcnt retires in issue order, so a
+// once the drains stopped deferring the first level's loads to the next tile
+// step (rounds 1-5; the pair-filter kernel's drains now make no global load
+// at all, the first level runs in flush_pending): vmcnt retires in issue order, so a
 // step that consumed the words loaded at the end of the previous one also
 // waited for the tile issued after them, and two tiles in flight measured no
 // faster with the deferral (round 2; r07c).  The deferral itself was worth
@@ -1095,8 +1143,9 @@ __device__ __forceinline__ void resolve_pending(const ScanParams& p, WaveQueue& 
   }
 }
 
-// First-level check of the hits of up to 64 ring entries; survivors go to
-// the pending list.  kInLoop: a drain inside the tile loop (a full ring),
+// The hits of up to 64 ring entries, re-tested per position and thinned (the
+// filter's other role, or the first level: kOtherRole); survivors go to the
+// pending list.  kInLoop: a drain inside the tile loop (a full ring),
 // whose entries all lie in full tiles.
 template <int MODE, bool kInLoop = false>
 __device__ __forceinline__ void drain(const ScanParams& p, WaveQueue& q, uint32_t lane,
@@ -1155,8 +1204,16 @@ __device__ __forceinline__ void drain(const ScanParams& p, WaveQueue& q, uint32_
   // hits: the class code's wave-uniform values stay in SGPRs)
   if constexpr (kDrainClass<MODE>)
     dc = drain_classes<MODE>(p, q.kcv, S, eidx, m & kmask, kfirst & m, seg_start + off0);
-  if ((MODE == 0 || kByteKeys<MODE> || kByteKeyAblation<MODE>) && (p.len_mask & 6u) != 0u) {
+  if ((kOtherRole<MODE> || kByteKeys<MODE> || kByteKeyAblation<MODE>) && (p.len_mask & 6u) != 0u) {
     maybe = m;   // 1-/2-byte keys: no first level, every hit goes to the buckets
+  } else if (kOtherRole<MODE>) {
+    // the hits that pass the filter's other role too (about one in four; every
+    // key window does): LDS only, the first level waits for the flush
+    while (m) {
+      const uint32_t j = (uint32_t)__builtin_ctz(m);
+      m &= m - 1;
+      maybe |= (uint32_t)other_role_pass(window4(ent, j), j) << j;
+    }
   } else {
     while (m) {
       const uint32_t j = (uint32_t)__builtin_ctz(m);
