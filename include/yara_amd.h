@@ -573,7 +573,8 @@ int yr_amd_scan_block_matches(
  * one entry per distinct (string, offset), the first record in record order
  * supplying length and pool_index.
  *
- * The device keeps the set of bytes_matched values in a 64-position window.
+ * The device keeps the set of bytes_matched values in a 64-position window,
+ * unless yr_amd_scanner_set_hex_wide (below) lifts that.
  * A record it cannot measure exactly -- a set wider than that or within reach
  * of YR_RE_SCAN_LIMIT, a pool entry without forward program, after
  * yr_amd_scan_window a byte either run may read outside the window -- goes to
@@ -589,7 +590,19 @@ int yr_amd_scan_block_matches(
  * YR_AMD_MATCH_MAX_RECORDS matches-to-be are refused likewise.  The batch
  * calls (yr_amd_match_batch_device, yr_amd_scan_batch_matches) ignore this
  * setting: they have one of their own, yr_amd_scanner_set_batch_match_classes
- * below, and settle literal strings only until that one says otherwise.
+ * below, and settle literal strings only until that one says otherwise.  The
+ * batch calls never read yr_amd_scanner_set_hex_wide either.
+ *
+ * yr_amd_scanner_set_hex_wide(1): a record whose set leaves the 64-position
+ * window, or comes within reach of YR_RE_SCAN_LIMIT, is measured by a wave-wide
+ * path that holds the whole domain of yr_re_fast_exec (bytes_matched 0 ..
+ * YR_RE_SCAN_LIMIT), so a jump or a sum of jumps of any width the compiler
+ * emits is measured exactly and one record can be up to 4097 matches.  One
+ * case stays in the rest: a FORWARD program that executes a jump with max > min
+ * on more than one live position -- there the reference returns the first
+ * element of a list that need not ascend (re.c:2302-2365, 2392-2400), which the
+ * set does not tell.  The other reasons above (no forward program, a window
+ * that does not hold the bytes, nothing found) are unchanged.
  *
  * yr_amd_tables_match_strings: out[k] = 1 iff string k is in one of the
  * classes.  Host code with the preconditions of yr_amd_tables_final_strings,
@@ -598,6 +611,11 @@ int yr_amd_scan_block_matches(
 #define YR_AMD_MATCH_LITERAL 1u
 #define YR_AMD_MATCH_HEX 2u
 int yr_amd_scanner_set_match_classes(yr_amd_scanner* scanner, uint32_t classes);
+/* 0 (default): a final hex record whose set leaves the 64-position window stays in the rest.
+ * 1: such records are measured by the wave-wide path.  Only read when the scanner's match
+ * classes include YR_AMD_MATCH_HEX; the set of strings (yr_amd_tables_match_strings) is
+ * unchanged.  NULL scanner or a value other than 0/1: YR_AMD_INVALID_ARGUMENT. */
+int yr_amd_scanner_set_hex_wide(yr_amd_scanner* scanner, int enable);
 int yr_amd_tables_match_strings(
     const yr_amd_tables* tables,
     uint32_t classes,

@@ -24,6 +24,18 @@ with the hex strings' records starts with their D2H (the rest of the LITERAL
 call, almost all of them hex records), timed here on the host's clock; the
 host's re-verification of every such record comes on top, so the D2H alone is
 a LOWER BOUND of that path.
+
+    python tools/match_rate.py --hex-wide [--gib 1] [--reps 10] [--out profiles/hex_wide_rates.json]
+
+The wave-wide path (yr_amd_scanner_set_hex_wide), classes LITERAL | HEX, the
+setting off and on alternating in one process, medians of --reps after a
+warm-up with min..max.  Two inputs of --gib: config C's planted input, whose
+rules hold no jump wider than 63 -- no record is queued, the difference is what
+the setting costs by itself (four launches more) -- and zeros with 4096 copies
+of the hexwide fixture's `back` string ({ B5 [0-100] B1 B2 B3 B4 }, 1 to 100
+starts each) under that fixture's tables: every record is wide, the difference
+over the records is the time per wide record.  The D2H of the rest with the
+setting off is again the lower bound of what a caller does without it.
 """
 import argparse
 import json
@@ -117,6 +129,90 @@ def hex_leg(a):
     sc.close()
 
 
+def hex_wide_leg(a):
+    import ctypes
+    import numpy as np
+    import torch
+    import yara_amd
+    from yara_amd import _hip, _lib
+    sys.path[:0] = [os.path.join(REPO, "tests", "golden")]
+    import gen_rules
+    import oracle
+    import planted
+    n = int(a.gib * (1 << 30))
+    golden = os.path.join(REPO, "tests", "golden")
+    stream = torch.cuda.Stream()
+    med = lambda v: round(statistics.median(v), 4)   # noqa: E731
+    span = lambda v: [round(min(v), 4), round(max(v), 4)]   # noqa: E731
+    out = {"bytes": n, "reps": a.reps, "classes": "LITERAL | HEX", "inputs": {}}
+    for name in ("C planted", "hexwide planted"):
+        if name == "C planted":
+            host = planted.planted_buffer(oracle.xorshift, gen_rules.gen("C"), n, 3)
+            path = os.path.join(golden, "tables", "C.npz")
+        else:
+            host = np.zeros(n, np.uint8)
+            for k in range(4096):   # B5 x (1 + k % 100), then the atom
+                at = (k + 1) * (n // 4100)
+                host[at - 1 - k % 100:at] = 0xB5
+                host[at:at + 4] = (0xB1, 0xB2, 0xB3, 0xB4)
+            path = os.path.join(golden, "hexwide", "tables.npz")
+        buf = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+        buf[:n] = torch.from_numpy(host).cuda()
+        del host
+        torch.cuda.synchronize()
+        sc = yara_amd.Scanner(yara_amd.Tables.from_npz(path, strings=True),
+                              stream=stream.cuda_stream)
+        sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+        sc.scan_device(buf.data_ptr(), n)
+        sc.device_result()
+
+        def stage(wide):   # (ms, n_matches, n_rest, rest pointer): the device call alone
+            sc.set_hex_wide(wide)
+            pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
+            nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            _lib.check("yr_amd_match_device", _lib.lib().yr_amd_match_device(
+                sc._h, 0, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr), ctypes.byref(nr)))
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1), nm.value, nr.value, pr.value
+
+        for _ in range(2):   # warm-up: buffers grown, clocks up
+            stage(False)
+            stage(True)
+        off, on, copy = [], [], []
+        for _ in range(a.reps):   # interleaved
+            ms, m_off, r_off, ptr = stage(False)
+            off.append(ms)
+            t1 = time.perf_counter()
+            recs = np.zeros(r_off, dtype=_lib.VERIFY_REC_DTYPE)
+            if r_off:
+                _hip.memcpy(recs.ctypes.data, ptr, r_off * 16, 2)
+            copy.append((time.perf_counter() - t1) * 1e3)
+            ms, m_on, r_on, _ = stage(True)
+            on.append(ms)
+        wide_records = r_off - r_on
+        out["inputs"][name] = {
+            "records": sc.verify_device(0)[1],
+            "off": {"matches": m_off, "rest": r_off, "match_device_ms": med(off),
+                    "min_max_ms": span(off)},
+            "on": {"matches": m_on, "rest": r_on, "match_device_ms": med(on),
+                   "min_max_ms": span(on)},
+            "added_ms": round(med(on) - med(off), 4), "wide_records": wide_records,
+            "us_per_wide_record": round((med(on) - med(off)) * 1e3 / wide_records, 4)
+            if wide_records else None,
+            "host_d2h_of_rest_off_ms": med(copy), "host_d2h_min_max_ms": span(copy),
+        }
+        print(name, json.dumps(out["inputs"][name]), flush=True)
+        sc.close()
+        del buf
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="C,short")
@@ -125,7 +221,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--hex", action="store_true",
                     help="the hex class on config C's planted input instead of the sets")
+    ap.add_argument("--hex-wide", action="store_true",
+                    help="the wave-wide path: the setting off and on, on C's planted input and "
+                         "on planted copies of the hexwide fixture's `back` string")
     a = ap.parse_args()
+    if a.hex_wide:
+        return hex_wide_leg(a)
     if a.hex:
         return hex_leg(a)
     import numpy as np

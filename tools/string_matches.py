@@ -1,6 +1,6 @@
 """Which literal strings of a compiled rules file match where in a file.
 
-    python tools/string_matches.py [--hex] RULES.yarc FILE [FILE ...]
+    python tools/string_matches.py [--hex | --hex-wide] RULES.yarc FILE [FILE ...]
 
 Prints one "string offset length xor" line per match of a final string
 (include/yara_amd.h: literal, not a chain part, not base64) -- absolute file
@@ -34,6 +34,14 @@ regexps, chain parts and base64 strings (and hex calls whose jumps span more
 than 64 positions).  Several files go through batches as without --hex
 (yr_amd_scanner_set_batch_match_classes): only the files above BLOCK bytes take
 the block path.
+
+--hex-wide: --hex, and on the block path (one file, or a file above BLOCK
+bytes) the wave-wide path too (yr_amd_scanner_set_hex_wide): hex calls whose
+jumps span more than 64 positions are measured as well, whatever the jumps'
+width.  What is left of them are forward programs that run a jump from several
+positions at once, whose match length the reference takes from its list's
+order.  Batches do not read the setting: files that go through them are
+settled as with --hex.
 """
 import gzip
 import os
@@ -83,8 +91,9 @@ def arenas(sizes):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--hex"]
+    argv = [a for a in sys.argv[1:] if a not in ("--hex", "--hex-wide")]
     hex_class = len(argv) != len(sys.argv) - 1
+    hex_wide = "--hex-wide" in sys.argv[1:]
     if len(argv) < 2:
         sys.exit(__doc__)
     import numpy as np
@@ -96,6 +105,7 @@ def main():
     if hex_class:
         sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
         sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+    sc.set_hex_wide(hex_wide)
     paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))

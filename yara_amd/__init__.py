@@ -270,6 +270,7 @@ class Scanner:
         self._batch_n = 0   # buffers of the last scan_batch_device
         self._classes = MATCH_LITERAL   # set_match_classes
         self._batch_classes = MATCH_LITERAL   # set_batch_match_classes
+        self._hex_wide = False   # set_hex_wide
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -344,16 +345,34 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_match_classes(self._h, classes))
         self._classes = classes
 
-    def _with_hex(self, hex, call):
-        # hex=True: this call with the hex class added, the scanner's setting restored
-        was = self._classes
+    def set_hex_wide(self, enable: bool):
+        """The wave-wide path of the hex class (yr_amd_scanner_set_hex_wide): a
+        record whose position set leaves the 64-position window is measured
+        too.  Read only while the classes include MATCH_HEX; the batch calls
+        never read it."""
+        _lib.check("yr_amd_scanner_set_hex_wide",
+                   _lib.lib().yr_amd_scanner_set_hex_wide(self._h, int(enable)))
+        self._hex_wide = bool(enable)
+
+    def _with_hex(self, hex, call, wide=False):
+        # hex=True: this call with the hex class added (wide=True: and the
+        # wave-wide path on), the scanner's settings restored
+        was, was_wide = self._classes, self._hex_wide
         if not hex or (was & MATCH_HEX):
-            return call()
-        self.set_match_classes(was | MATCH_HEX)
+            hex = False
+        if not wide or was_wide:
+            wide = False
+        if hex:
+            self.set_match_classes(was | MATCH_HEX)
+        if wide:
+            self.set_hex_wide(True)
         try:
             return call()
         finally:
-            self.set_match_classes(was)
+            if wide:
+                self.set_hex_wide(False)
+            if hex:
+                self.set_match_classes(was)
 
     def set_batch_match_classes(self, classes: int):
         """The string classes the BATCH match stage settles
@@ -374,7 +393,7 @@ class Scanner:
         finally:
             self.set_batch_match_classes(was)
 
-    def match_device(self, data_base: int = 0, hex: bool = False):
+    def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
         copied to the host: ``matches`` {offset, string, length, xor_key,
         pool_index}, one per distinct (string, offset) of the final strings
@@ -385,8 +404,11 @@ class Scanner:
         ``hex=True`` settles the final hex strings too for this call
         (Tables.match_strings(MATCH_LITERAL | MATCH_HEX)): a call of one can
         be several matches; ``hex=False`` leaves the scanner's classes
-        (set_match_classes) as they are."""
-        return self._with_hex(hex, lambda: self._match_device(data_base))
+        (set_match_classes) as they are.  ``wide=True`` turns the wave-wide
+        path of the hex class on for this call (set_hex_wide): by itself it
+        implies nothing, it goes with ``hex=True`` or a scanner whose classes
+        hold MATCH_HEX."""
+        return self._with_hex(hex, lambda: self._match_device(data_base), wide)
 
     def _match_device(self, data_base):
         from ._hip import memcpy
@@ -403,12 +425,13 @@ class Scanner:
             memcpy(rest.ctypes.data, pr.value, nr.value * 16, 2)
         return matches, rest
 
-    def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False):
+    def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False,
+                       wide: bool = False):
         """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
         see match_device.  For the final strings ``matches`` is what stock
         libyara's match lists hold after scanning this block alone; the blocks
         of one scan merge with ``merge_matches``."""
-        return self._with_hex(hex, lambda: self._string_matches(data, data_base))
+        return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide)
 
     def _string_matches(self, data, data_base):
         d = _arr(data, np.uint8)

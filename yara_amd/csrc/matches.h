@@ -207,4 +207,34 @@ hipError_t launch_batch_hex_offsets(const BatchHexParams& p, int matches, hipStr
 // record's buffer differs from its predecessor's.
 hipError_t launch_batch_hex_unique(const BatchHexParams& p, int pass, hipStream_t s);
 
+// ---- The wave-wide path of the hex class (yr_amd_scanner_set_hex_wide) ----
+// A record whose set leaves HexSet's 64 positions is measured by one WAVE: the
+// whole domain of yr_re_fast_exec, bytes_matched 0 .. YR_RE_SCAN_LIMIT, is 64
+// lanes x 64 bits, word l of the set in lane l, plus one bit for the value
+// YR_RE_SCAN_LIMIT itself (a consuming opcode at 4095).  The measure pass
+// queues such records; their backward sets go to wsets by queue slot, word
+// kWideWords - 1 holding that last bit.  In sets[] a wide match is marked by
+// mask 0, pad 1: it has no item for the lane-per-record expansion.
+constexpr uint32_t kWideWords = 65;
+// A struct of its own: HexMatchParams is a kernel argument of the kernels
+// above, which stay what they are.
+struct HexWideParams {
+  HexMatchParams h;
+  uint32_t* queue;              // [qcap] the queued records, in no particular order
+  uint32_t* qlen;               // records appended; above qcap: the host grows and runs again
+  uint32_t qcap;
+  uint64_t* qlen_out;           // qlen for the host (pinned)
+  uint64_t* wsets;              // [qcap][kWideWords]
+  uint32_t* icount;             // [h.m.n] items by record
+  uint32_t* istart;             // [h.m.n] the items of the records below it in its wave
+};
+
+// The measure pass with the queue: launch_hex_measure's outputs + icount, then
+// one wave per queued record (a fixed grid of `waves` waves strides over the
+// queue: no wait for its length), then the per-wave counts again from the
+// per-record arrays, + istart.
+hipError_t launch_hex_wide_measure(const HexWideParams& w, uint32_t waves, hipStream_t s);
+// launch_hex_expand by istart, then the wide records' items, one wave each.
+hipError_t launch_hex_wide_expand(const HexWideParams& w, uint32_t waves, hipStream_t s);
+
 }  // namespace yamd

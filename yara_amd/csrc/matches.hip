@@ -32,6 +32,9 @@
 // the sort runs over the items (matches.h HexMatchParams).
 // A batch with the hex class (yr_amd_scanner_set_batch_match_classes) counts
 // its CSR over the items: the batch_hex_* kernels (BatchHexParams, 18.3).
+// With yr_amd_scanner_set_hex_wide the records whose set leaves hex_run's 64
+// positions are queued and measured one WAVE each, the whole 4096-position
+// set across the lanes: the hex_wide_* kernels (HexWideParams, 18.4).
 //
 // The comparisons are restated here rather than shared with verify.hip: that
 // file's kernels stay byte for byte what they were (their register budgets are
@@ -449,6 +452,8 @@ __device__ __forceinline__ uint32_t hex_stage_code(const uint8_t* code, uint32_t
 }
 
 constexpr int kHexNone = 0, kHexMatch = 1, kHexUndecided = 2;
+// (WIDE only) undecided because the set leaves the window: the wave-wide path decides
+constexpr int kHexWide = 3;
 
 // yr_re_fast_exec (re.c:2150-2423) in position-set form, verify.hip
 // fast_re_set's transitions, but with the set at RE_OPCODE_MATCH as the
@@ -458,7 +463,7 @@ constexpr int kHexNone = 0, kHexMatch = 1, kHexUndecided = 2;
 // the 64-position window or come near YR_RE_SCAN_LIMIT, an opcode outside the
 // fast set, a program that does not end in MATCH, or a REPEAT_ANY right
 // before MATCH (whose b + min the reference does not bound).
-template <class Code>
+template <class Code, bool WIDE = false>
 __device__ int hex_run(const Code code, uint32_t len, const uint8_t* __restrict__ input, int maxb,
                        bool backwards, HexSet& out) {
   int base = 0;
@@ -481,7 +486,11 @@ __device__ int hex_run(const Code code, uint32_t len, const uint8_t* __restrict_
       const int lo = __builtin_ctzll(live), hi = 63 - __builtin_clzll(live);
       const int span = hi - lo + (mx - mn);
       const int nb = base + lo + mn;
-      if (span > 63 || nb + span >= kReScanLimit) return kHexUndecided;
+      if (span > 63 || nb + span >= kReScanLimit) return WIDE ? kHexWide : kHexUndecided;
+      // (with the wave-wide path on: a forward jump with 0 < min < max run from
+      // several positions leaves the reference's list unsorted -- hex_wide_run's
+      // note -- and the lowest bit need not be its first element: undecided)
+      if (WIDE && !backwards && mn > 0 && mx > mn && (live & (live - 1)) != 0) return kHexUndecided;
       // t | t << 1 | ... | t << (mx - mn), by doubling
       uint64_t acc = live >> lo;
       const int r = mx - mn + 1;   // copies
@@ -529,19 +538,21 @@ __device__ int hex_run(const Code code, uint32_t len, const uint8_t* __restrict_
 // _yr_scan_verify_re_match (scan.c:778-885) of a final hex string's record:
 // kHexMatch with m.length = F, the forward program's smallest bytes_matched,
 // and the backward program's set in `set` ({0} without one).
-template <class Code>
+template <class Code, bool WIDE = false>
 __device__ int hex_call(const MatchParams& p, const DevRe& r, const Code fwd, const Code bwd,
                         uint64_t offset, MatchMeasure& m, HexSet& set) {
   const uint8_t* d = p.data + offset;
   HexSet f;
-  int v = hex_run(fwd, r.fwd_len, d, (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit),
-                  false, f);
+  int v = hex_run<Code, WIDE>(fwd, r.fwd_len, d,
+                              (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit), false, f);
   if (v != kHexMatch) return v;
   m.length = f.base + (uint32_t)__builtin_ctzll(f.mask);   // the first of the ascending list
   if (r.bwd_len == 0) return m.length != 0 ? kHexMatch : kHexNone;
-  return hex_run(bwd, r.bwd_len, d, (int)min<uint64_t>(offset, (uint64_t)kReScanLimit), true, set);
+  return hex_run<Code, WIDE>(bwd, r.bwd_len, d, (int)min<uint64_t>(offset, (uint64_t)kReScanLimit),
+                             true, set);
 }
 
+template <bool WIDE = false>
 __device__ int measure_hex(const HexMatchParams& q, const DevPoolRec& e, uint64_t offset,
                            uint32_t codebuf, MatchMeasure& m, HexSet& set) {
   const MatchParams& p = q.m;
@@ -560,9 +571,10 @@ __device__ int measure_hex(const HexMatchParams& q, const DevPoolRec& e, uint64_
   // (contiguous in the blob: both programs staged at once when they fit)
   if (r.bwd_len == 0 || r.bwd_off == r.fwd_off + r.fwd_len) {
     const uint32_t at = hex_stage_code(fwd, r.fwd_len + r.bwd_len, codebuf);
-    if (at != kNoLds) return hex_call(p, r, LdsCode{at}, LdsCode{at + r.fwd_len}, offset, m, set);
+    if (at != kNoLds)
+      return hex_call<LdsCode, WIDE>(p, r, LdsCode{at}, LdsCode{at + r.fwd_len}, offset, m, set);
   }
-  return hex_call(p, r, GlobalCode{fwd}, GlobalCode{bwd}, offset, m, set);
+  return hex_call<GlobalCode, WIDE>(p, r, GlobalCode{fwd}, GlobalCode{bwd}, offset, m, set);
 }
 
 // The inclusive prefix sum of v over the wave's lanes.
@@ -791,6 +803,401 @@ __global__ __launch_bounds__(256) void batch_hex_offsets_kernel(BatchHexParams b
   (MATCHES ? b.match_off : b.item_off)[k] = o;
 }
 
+// ---- The wave-wide path of the hex class (matches.h HexWideParams) ----
+
+// hex_measure_kernel's twin with the queue: a record that hex_run gives up on
+// for WIDTH (kHexWide) is a rest record here, as it is there, and its index is
+// appended to the queue -- one ballot and one atomic add per wave, then
+// lane-wise stores.  (A twin: hex_measure_kernel stays what it is.)
+__global__ __launch_bounds__(256) void hex_measure_queue_kernel(HexWideParams w) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const HexMatchParams& q = w.h;
+  const MatchParams& p = q.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool wide = false;
+  if (r < p.n) {
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      const int v = measure_hex<true>(q, e, rec.offset, buf, m, set);
+      is_match = v == kHexMatch;
+      wide = v == kHexWide;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(p, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? p.pool_string[rec.pool_index] : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    q.sets[r] = set;
+    w.icount[r] = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  const uint64_t qmask = __ballot(wide);
+  if (qmask != 0) {   // (wave-uniform)
+    uint32_t at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(w.qlen, (uint32_t)__popcll(qmask));
+    at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(qmask);
+    if (wide && at < w.qcap) w.queue[at] = (uint32_t)r;
+  }
+  // (the per-wave counts are hex_wide_recount_kernel's: they include the wide results)
+}
+
+__global__ void hex_wide_clear_kernel(HexWideParams w) { *w.qlen = 0; }
+
+constexpr uint32_t kWideSlice = 4096 + 16;   // a wave's input bytes: a run's reach + the alignment head
+constexpr uint32_t kWideCode = 512;          // a wave's staged program
+constexpr int kWideTop = 4096;               // the bytes_matched value of the set's 65th word
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64);
+  const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
+  return (uint64_t)hi << 32 | lo;
+}
+
+// The 4096-bit set << d: w'[l] = w[l - d / 64] << (d % 64) | w[l - d / 64 - 1]
+// >> (64 - d % 64).  Every lane of the wave calls it.
+__device__ __forceinline__ uint64_t wide_shl(uint64_t w, uint32_t d) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int q = (int)(d >> 6), s = (int)(d & 63u);
+  if (q >= 64) return 0;
+  const uint64_t a = shfl64(w, (lane - q) & 63), b = shfl64(w, (lane - q - 1) & 63);
+  const uint64_t hi = lane >= q ? a : 0ull, lo = lane >= q + 1 ? b : 0ull;
+  return s == 0 ? hi : (hi << s | lo >> (64 - s));
+}
+
+// The bits of w below position maxb (lane l holds the positions [64 l, 64 l + 64)).
+__device__ __forceinline__ uint64_t wide_live(uint64_t w, int maxb) {
+  const int lim = maxb - 64 * (int)(threadIdx.x & 63u);
+  return lim >= 64 ? w : (lim <= 0 ? 0ull : w & ((1ull << lim) - 1));
+}
+
+// One run's input in the wave's LDS slice: byte j of the slice is input byte b
+// = j - head, forwards the memory from the 16-byte boundary at or below the
+// record's offset on, backwards the memory below the boundary at or above it,
+// REVERSED -- so both directions read alike.  Staged 1 KiB a pass (lane l the
+// 16 bytes at (64 i + l) 16, one aligned load where all 16 lie in [lo, hi), the
+// bytes that do one by one otherwise), and only the passes that hold a live
+// position.
+struct WideInput {
+  uint8_t* slice;         // LDS
+  const uint8_t* org;     // the boundary
+  const uint8_t* lo;      // what may be loaded: [lo, hi)
+  const uint8_t* hi;
+  uint32_t head;          // input byte 0 in the slice
+  uint32_t chunks;        // 16-byte chunks that hold a byte below max_bytes_matched
+  uint32_t staged;        // chunks staged (a multiple of 64)
+  bool backwards;
+
+  __device__ void open(uint8_t* lds, const uint8_t* input, int maxb, bool back, const uint8_t* l,
+                       const uint8_t* h) {
+    slice = lds;
+    backwards = back;
+    lo = l;
+    hi = h;
+    const uintptr_t a = (uintptr_t)input;
+    const uintptr_t o = back ? (a + 15) & ~(uintptr_t)15 : a & ~(uintptr_t)15;
+    org = (const uint8_t*)o;
+    head = (uint32_t)(back ? o - a : a - o);
+    chunks = (head + (uint32_t)maxb + 15) / 16;
+    staged = 0;
+  }
+
+  // Input bytes [0, need) are in the slice afterwards (need <= max_bytes_matched).
+  __device__ void ensure(uint32_t need) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const uint32_t want = (head + need + 15) / 16;
+    if (staged >= want) return;
+    while (staged < want) {
+      const uint32_t c = staged + (threadIdx.x & 63u);
+      if (c < chunks) {
+        const uint8_t* g = backwards ? org - 16 * (uintptr_t)(c + 1) : org + 16 * (uintptr_t)c;
+        u32x4 v;
+        if (g >= lo && g + 16 <= hi) {
+          const u32x4 m = *reinterpret_cast<const u32x4*>(g);
+          if (backwards) {
+            v.x = __builtin_bswap32(m.w);
+            v.y = __builtin_bswap32(m.z);
+            v.z = __builtin_bswap32(m.y);
+            v.w = __builtin_bswap32(m.x);
+          } else {
+            v = m;
+          }
+        } else {
+          uint32_t d[4] = {0, 0, 0, 0};
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const uint8_t* a = backwards ? g + 15 - j : g + j;
+            const uint32_t byte = (a >= lo && a < hi) ? *a : 0u;
+            d[j / 4] |= byte << (8 * (j % 4));
+          }
+          v.x = d[0];
+          v.y = d[1];
+          v.z = d[2];
+          v.w = d[3];
+        }
+        *reinterpret_cast<u32x4*>(slice + 16 * c) = v;
+      }
+      staged += 64;
+    }
+    // (one wave writes and reads the slice: LDS serves a wave's requests in order)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+
+  // Bit i: this lane's i-th input byte c passes ((c & mask) == val) != neg.
+  // SWAR over 16 dwords: the exact zero-byte flags of (x & mask4) ^ val4.
+  __device__ uint64_t pass(uint32_t mask, uint32_t val, bool neg) const {
+    const uint32_t at = head + 64 * (threadIdx.x & 63u);
+    const uint32_t* dw = reinterpret_cast<const uint32_t*>(slice) + (at >> 2);
+    const uint32_t sh = at & 3u, mask4 = mask * 0x01010101u, val4 = val * 0x01010101u;
+    uint64_t out = 0;
+    uint32_t prev = dw[0];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const uint32_t next = dw[i + 1];
+      const uint32_t x = __builtin_amdgcn_alignbyte(next, prev, sh);
+      prev = next;
+      const uint32_t t = (x & mask4) ^ val4;
+      // 0x80 in every byte of t that is zero, no borrow between bytes
+      uint32_t z = ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
+      // the four flags (bits 7, 15, 23, 31) side by side
+      uint32_t f = (((z >> 7) * 0x00204081u) >> 21) & 0xFu;
+      if (neg) f ^= 0xFu;
+      out |= (uint64_t)f << (4 * i);
+    }
+    return out;
+  }
+};
+
+// hex_run's rule on the whole domain (matches.h): w = this lane's word of the
+// set at MATCH, top = the value YR_RE_SCAN_LIMIT is in it.  Wave-uniform
+// control flow: every lane runs every step.  A consuming opcode is S' = ((S n
+// live) n pass) << 1, the carry of a word from the lane below; REPEAT_ANY {mn,
+// mx} is S' = OR_d (S n live) << d over d = mn .. mx, smeared by doubling, cut
+// to the positions below max_bytes_matched (re.c:2314; the b + mn copy at or
+// past it dies at the next opcode, which is not MATCH).
+// *ordered: forwards the reference returns the first element of its LIST to
+// reach MATCH (re.c:2392-2400), and the list ascends only while one live
+// position builds it: with live positions a < b, a's new positions are placed
+// by comparison with b's pointer BEFORE b advances by mn (re.c:2302-2365), so
+// b + mn can stand in front of smaller values.  A forward REPEAT_ANY with mx >
+// mn on more than one live position leaves the order to the host: undecided.
+template <class Code>
+__device__ int hex_wide_run(const Code code, uint32_t len, WideInput& in, int maxb, bool backwards,
+                            uint64_t& w, bool& top) {
+  const uint32_t lane = threadIdx.x & 63u;
+  w = lane == 0 ? 1ull : 0ull;
+  top = false;
+  uint32_t ip = 0;
+  while (ip < len) {
+    const uint32_t op = uniform(code[ip]), b1 = uniform(code[ip + 1]), b2 = uniform(code[ip + 2]);
+    if (op == kReMatch) return kHexMatch;   // (not empty: every transition returns on an empty set)
+    const uint64_t live = wide_live(w, maxb);   // (top: 4096 >= max_bytes_matched, dead)
+    const uint64_t busy = __ballot(live != 0);
+    if (busy == 0) return kHexNone;
+    if (op == kReRepeatAnyUngreedy) {
+      const uint32_t mn = b1 | (b2 << 8);
+      const uint32_t mx = uniform(code[ip + 3]) | (uniform(code[ip + 4]) << 8);
+      if (mx < mn || uniform(code[ip + 5]) == kReMatch) return kHexUndecided;
+      if (!backwards && mx > mn) {
+        const uint32_t n = wave_prefix((uint32_t)__popcll(live));
+        if ((uint32_t)__shfl((int)n, 63, 64) != 1) return kHexUndecided;
+      }
+      uint64_t acc = wide_shl(live, mn);
+      const uint32_t r = mx - mn + 1;   // copies
+      uint32_t have = 1;
+      while (2 * have <= r) {
+        acc |= wide_shl(acc, have);
+        have *= 2;
+      }
+      if (have < r) acc |= wide_shl(acc, r - have);
+      w = wide_live(acc, maxb);
+      top = false;
+      if (__ballot(w != 0) == 0) return kHexNone;
+      ip += 5;
+      continue;
+    }
+    uint32_t mask, val, sz;
+    bool neg = false;
+    switch (op) {
+      case kReAny: mask = 0; val = 0; sz = 1; break;
+      case kReLiteral: mask = 0xFF; val = b1; sz = 2; break;
+      case kReNotLiteral: mask = 0xFF; val = b1; sz = 2; neg = true; break;
+      case kReMaskedLiteral: mask = b2; val = b1; sz = 3; break;
+      case kReMaskedNotLiteral: mask = b2; val = b1; sz = 3; neg = true; break;
+      default: return kHexUndecided;
+    }
+    // the bytes of the highest live word's lane and below, none at or past maxb
+    const uint32_t top_lane = 63u - (uint32_t)__builtin_clzll(busy);
+    in.ensure(min((uint32_t)maxb, 64u * (top_lane + 1)));
+    uint64_t res = 0;
+    if (live != 0) res = live & in.pass(mask, val, neg);   // (a lane with nothing live skips)
+    const uint32_t out = (uint32_t)(res >> 63);
+    const uint32_t carry = (uint32_t)__shfl_up((int)out, 1, 64);
+    top = __shfl((int)out, 63, 64) != 0;
+    w = res << 1 | (lane == 0 ? 0u : carry);
+    if (__ballot(w != 0) == 0 && !top) return kHexNone;
+    ip += sz;
+  }
+  return kHexUndecided;
+}
+
+// One program of a wave's record into the wave's LDS when it fits (with the
+// operand bytes a read may reach past MATCH: the blob carries 64 bytes of padding).
+__device__ __forceinline__ bool wide_stage_code(const uint8_t* code, uint32_t len, uint8_t* buf) {
+  if (len + 8 > kWideCode) return false;
+  for (uint32_t i = threadIdx.x & 63u; i < len + 8; i += 64) buf[i] = code[i];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return true;
+}
+
+__device__ int hex_wide_program(const uint8_t* code, uint32_t len, uint8_t* codebuf, WideInput& in,
+                                int maxb, bool backwards, uint64_t& w, bool& top) {
+  if (wide_stage_code(code, len, codebuf))
+    return hex_wide_run(LdsCode{(uint32_t)(uintptr_t)codebuf}, len, in, maxb, backwards, w, top);
+  return hex_wide_run(GlobalCode{code}, len, in, maxb, backwards, w, top);
+}
+
+// One WAVE per queued record, the waves of a fixed grid striding over the
+// queue.  hex_call's two runs: F = the lowest position of the forward set, the
+// backward set to wsets.  A match overwrites what hex_measure_queue_kernel
+// left of the record: its key (the string in place of n_strings), F, the item
+// count, and the set's mark (mask 0, pad 1).  Anything else leaves the record
+// in the rest.  measure_hex's window test lies behind the record already;
+// [win_lo, win_hi) bounds every load.
+__global__ __launch_bounds__(256) void hex_wide_measure_kernel(HexWideParams q) {
+  __shared__ __attribute__((aligned(16))) uint8_t slices[4][kWideSlice];
+  __shared__ __attribute__((aligned(16))) uint8_t codes[4][kWideCode];
+  const MatchParams& p = q.h.m;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t n = min(*q.qlen, q.qcap);
+  const uint8_t* lo = p.data + p.win_lo;
+  const uint8_t* hi = p.data + p.win_hi;
+  for (uint32_t slot = blockIdx.x * 4 + wave; slot < n; slot += gridDim.x * 4) {
+    const uint32_t r = q.queue[slot];
+    const VerifyRec rec = p.recs[r];
+    const DevRe re = p.pool[rec.pool_index].re;
+    const uint64_t offset = rec.offset;
+    const uint8_t* d = p.data + offset;
+    WideInput in;
+    uint64_t w;
+    bool top;
+    int maxb = (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit);
+    in.open(slices[wave], d, maxb, false, lo, hi);
+    int v = hex_wide_program(q.h.re_code + re.fwd_off, re.fwd_len, codes[wave], in, maxb, false, w, top);
+    if (v != kHexMatch) continue;
+    const uint64_t ends = __ballot(w != 0);
+    uint32_t F = kWideTop;   // (top alone)
+    if (ends != 0) {
+      const int first = __builtin_ctzll(ends);
+      F = 64u * first + (uint32_t)__builtin_ctzll(shfl64(w, first) | 1ull << 63);
+    }
+    uint32_t items = 1;
+    w = lane == 0 ? 1ull : 0ull;   // (no backward program: {0})
+    top = false;
+    if (re.bwd_len == 0) {
+      if (F == 0) continue;
+    } else {
+      maxb = (int)min<uint64_t>(offset, (uint64_t)kReScanLimit);
+      in.open(slices[wave], d, maxb, true, lo, hi);
+      v = hex_wide_program(q.h.re_code + re.bwd_off, re.bwd_len, codes[wave], in, maxb, true, w, top);
+      if (v != kHexMatch) continue;
+      items = (uint32_t)__shfl((int)wave_prefix((uint32_t)__popcll(w)), 63, 64) + (top ? 1u : 0u);
+    }
+    uint64_t* ws = q.wsets + (uint64_t)slot * kWideWords;
+    ws[lane] = w;
+    if (lane == 0) {
+      ws[kWideWords - 1] = top ? 1ull : 0ull;
+      p.keys[r] = (uint64_t)p.pool_string[rec.pool_index] << 32 | (offset & 0xFFFFFFFFull);
+      p.meas[r] = MatchMeasure{F, 0u};
+      q.h.sets[r] = HexSet{0ull, 0u, 1u};
+      q.icount[r] = items;
+    }
+  }
+}
+
+// The per-wave counts of hex_measure_kernel, from the per-record arrays once
+// the wide records are in them, + each record's items' start within its wave.
+__global__ __launch_bounds__(256) void hex_wide_recount_kernel(HexWideParams w) {
+  const MatchParams& p = w.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r == 0) *w.qlen_out = *w.qlen;
+  bool rest = false;
+  uint32_t items = 0;
+  if (r < p.n) {
+    rest = (uint32_t)(p.keys[r] >> 32) == p.n_strings;
+    items = rest ? 0u : w.icount[r];
+  }
+  const uint64_t mask = __ballot(rest);
+  const uint32_t incl = wave_prefix(items);
+  const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
+  if (r < p.n) w.istart[r] = incl - items;
+  if ((threadIdx.x & 63u) == 0 && r < p.n) {
+    p.block_off[r / kGroup] = (uint64_t)__popcll(mask);
+    w.h.iblock_off[r / kGroup] = (uint64_t)total;
+  }
+}
+
+// hex_expand_kernel's twin: the start within the wave from istart (the lanes
+// below may be wide records); a wide match has mask 0, no item here.
+__global__ __launch_bounds__(256) void hex_expand_at_kernel(HexWideParams w) {
+  const HexMatchParams& q = w.h;
+  const MatchParams& p = q.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  const uint64_t key = p.keys[r];
+  const HexSet set = q.sets[r];
+  if (hex_items(key, p.n_strings, set) == 0) return;
+  const uint64_t g = r / kGroup;
+  uint64_t at = q.ichunk_off[g / kChunkGroups] + q.iblock_off[g] + w.istart[r];
+  const uint64_t offset = key & 0xFFFFFFFFull;
+  for (uint64_t x = set.mask; x != 0 && at < q.n_items; x &= x - 1, ++at) {
+    const uint32_t B = set.base + (uint32_t)__builtin_ctzll(x);
+    q.ikeys[at] = (key & 0xFFFFFFFF00000000ull) | (offset - B);
+    q.iindex[at] = (uint32_t)r;
+  }
+}
+
+// One wave per wide record: lane l expands word l at the record's start plus
+// the bits of the lanes below; the value YR_RE_SCAN_LIMIT comes last.
+__global__ __launch_bounds__(256) void hex_wide_expand_kernel(HexWideParams w) {
+  const HexMatchParams& q = w.h;
+  const MatchParams& p = q.m;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t n = min(*w.qlen, w.qcap);
+  for (uint32_t slot = blockIdx.x * 4 + (threadIdx.x >> 6); slot < n; slot += gridDim.x * 4) {
+    const uint32_t r = w.queue[slot];
+    if (q.sets[r].pad != 1u) continue;   // (not measured a match: a rest record)
+    const uint64_t key = p.keys[r];
+    const uint64_t* ws = w.wsets + (uint64_t)slot * kWideWords;
+    const uint64_t word = ws[lane];
+    const uint32_t bits = (uint32_t)__popcll(word);
+    const uint32_t incl = wave_prefix(bits);
+    const uint64_t g = r / kGroup;
+    const uint64_t start = q.ichunk_off[g / kChunkGroups] + q.iblock_off[g] + w.istart[r];
+    const uint64_t offset = key & 0xFFFFFFFFull;   // (B <= min(offset, YR_RE_SCAN_LIMIT))
+    uint64_t at = start + incl - bits;
+    for (uint64_t x = word; x != 0 && at < q.n_items; x &= x - 1, ++at) {
+      const uint32_t B = 64u * lane + (uint32_t)__builtin_ctzll(x);
+      q.ikeys[at] = (key & 0xFFFFFFFF00000000ull) | (offset - B);
+      q.iindex[at] = r;
+    }
+    if (lane == 63 && ws[kWideWords - 1] != 0 && start + incl < q.n_items) {
+      q.ikeys[start + incl] = (key & 0xFFFFFFFF00000000ull) | (offset - (uint64_t)kWideTop);
+      q.iindex[start + incl] = r;
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t launch_match_classify(const MatchParams& p, hipStream_t s) {
@@ -869,6 +1276,28 @@ hipError_t launch_hex_unique(const HexMatchParams& p, int pass, hipStream_t s) {
     hipLaunchKernelGGL(hex_unique_kernel<0>, match_grid(p.n_items), dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL(hex_unique_kernel<1>, match_grid(p.n_items), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_hex_wide_measure(const HexWideParams& w, uint32_t waves, hipStream_t s) {
+  const uint64_t n = w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || w.qcap == 0) return hipErrorInvalidValue;
+  // (a kernel, not a memset: the stage may be recorded into a graph)
+  hipLaunchKernelGGL(hex_wide_clear_kernel, dim3(1), dim3(1), 0, s, w);
+  hipLaunchKernelGGL(hex_measure_queue_kernel, match_grid(n), dim3(256), 0, s, w);
+  hipLaunchKernelGGL(hex_wide_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, w);
+  hipLaunchKernelGGL(hex_wide_recount_kernel, match_grid(n), dim3(256), 0, s, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_hex_wide_expand(const HexWideParams& w, uint32_t waves, hipStream_t s) {
+  const HexMatchParams& p = w.h;
+  if (p.m.n == 0 || p.n_items == 0) return hipSuccess;
+  if (p.m.n > kMatchMaxRecords || p.n_items > kMatchMaxRecords || waves == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hex_expand_at_kernel, match_grid(p.m.n), dim3(256), 0, s, w);
+  hipLaunchKernelGGL(hex_wide_expand_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, w);
   return hipGetLastError();
 }
 

@@ -226,7 +226,7 @@ struct yr_amd_scanner {
   size_t mhist_cap = 0;
   uint64_t* d_mhchunk = nullptr;
   size_t mhchunk_cap = 0;
-  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items}
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued}
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
@@ -254,6 +254,15 @@ struct yr_amd_scanner {
   size_t hblock_cap = 0;
   uint64_t* d_hchunk = nullptr;         // [2 * (chunks + 1)]
   size_t hchunk_cap = 0;
+  // the wave-wide path of the hex class (yr_amd_scanner_set_hex_wide; matches.h
+  // HexWideParams)
+  bool hex_wide = false;
+  uint32_t* d_wqueue = nullptr;         // [1 + cap]: the queue's length, the queued records
+  size_t wqueue_cap = 0;
+  uint64_t* d_wsets = nullptr;          // [cap * kWideWords] the backward sets by queue slot
+  size_t wsets_cap = 0;
+  uint32_t* d_wcount = nullptr;         // [2 * cap]: items by record, their starts within the wave
+  size_t wcount_cap = 0;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -551,7 +560,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_mout, (void*)s->d_mblock, (void*)s->d_mchunk, (void*)s->d_mhist,
                   (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff, (void*)s->d_hkeys,
                   (void*)s->d_hmeas, (void*)s->d_hsets, (void*)s->d_hrest, (void*)s->d_hblock,
-                  (void*)s->d_hchunk})
+                  (void*)s->d_hchunk, (void*)s->d_wqueue, (void*)s->d_wsets, (void*)s->d_wcount})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1731,7 +1740,7 @@ int reallocate(T*& p, size_t need) {
 // two CSR offset arrays too.
 int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (s->h_msum == nullptr) {
-    if (hipHostMalloc((void**)&s->h_msum, 4 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
+    if (hipHostMalloc((void**)&s->h_msum, 5 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
       s->h_msum = nullptr;
       return YR_AMD_INSUFFICIENT_MEMORY;
     }
@@ -1779,6 +1788,7 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   if (!r) r = grow_geo(s->d_hchunk, s->hchunk_cap, 2 * chunks);
   if (r) return r;
   HexMatchParams p{};
+  HexWideParams w{};
   p.m.data = s->last.data;
   p.m.size = s->last.block_size;
   p.m.win_lo = s->win_lo;
@@ -1801,16 +1811,50 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   p.iblock_off = s->d_hblock + groups;
   p.ichunk_off = s->d_hchunk + chunks;
   const KeptLists none{{0, 0, 0, 0}};
-  // measure -> the offsets of the rest and of the items -> the rest; wait
-  HIP_TRY(launch_hex_measure(p, s->stream));
-  HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
-  HIP_TRY(launch_block_offsets(p.iblock_off, p.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
-                               s->stream));
-  HIP_TRY(launch_match_rest(p.m, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  // The wave-wide path: the records the lane-per-record measure gives up on for
+  // width are queued and measured one wave each, a fixed grid of a few waves per
+  // CU striding over the queue -- its length is not waited for.  Should it pass
+  // the queue's capacity, the wait below sees that and the pass runs again with
+  // a larger queue: the capacity follows the wide records, not the records.
+  const bool wide = s->hex_wide;
+  const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
+  uint64_t queued = 0;
+  for (size_t qcap = std::max<size_t>(s->wqueue_cap, 257) - 1;; qcap = std::max<size_t>(queued, 2 * qcap)) {
+    if (wide) {
+      r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + qcap);
+      if (!r) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
+      if (!r) r = grow_geo(s->d_wcount, s->wcount_cap, 2 * n);
+      if (r) return r;
+      w.h = p;
+      w.qlen = s->d_wqueue;
+      w.queue = s->d_wqueue + 1;
+      w.qcap = (uint32_t)std::min<size_t>(s->wqueue_cap - 1, kMatchMaxRecords);
+      w.qlen_out = s->d_mhsum + 4;
+      w.wsets = s->d_wsets;
+      w.icount = s->d_wcount;
+      w.istart = s->d_wcount + n;
+    }
+    // measure -> the offsets of the rest and of the items -> the rest; wait
+    if (wide)
+      HIP_TRY(launch_hex_wide_measure(w, wide_waves, s->stream));
+    else
+      HIP_TRY(launch_hex_measure(p, s->stream));
+    HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
+    HIP_TRY(launch_block_offsets(p.iblock_off, p.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
+                                 s->stream));
+    HIP_TRY(launch_match_rest(p.m, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    queued = wide ? s->h_msum[4] : 0;
+    if (queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    if (!wide || queued <= w.qcap) break;
+  }
   *nr = s->h_msum[0];
   const uint64_t items = s->h_msum[3];
-  if (*nr > n || items > 64 * (n - *nr)) return YR_AMD_INTERNAL_FATAL_ERROR;
+  if (*nr > n || items > 64 * (n - *nr) + ((uint64_t)kReScanLimit + 1) * queued)
+    return YR_AMD_INTERNAL_FATAL_ERROR;
+  if (debug_level() >= 1 && wide)
+    fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_device()\n",
+            (unsigned long long)n, (unsigned long long)queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   *nm = 0;
   if (items == 0) return YR_AMD_SUCCESS;
@@ -1829,7 +1873,12 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort; distinct keys -> their offsets -> the matches; wait
-  HIP_TRY(launch_hex_expand(p, s->stream));
+  if (wide) {
+    w.h = p;
+    HIP_TRY(launch_hex_wide_expand(w, wide_waves, s->stream));
+  } else {
+    HIP_TRY(launch_hex_expand(p, s->stream));
+  }
   int sorted = 0;
   HIP_TRY(match_sort(keys, index, items, lo_bits, hi_bits, s->d_mhist, s->d_mhchunk, s->d_mhsum + 2,
                      s->stream, &sorted));
@@ -1852,6 +1901,12 @@ int yr_amd_scanner_set_match_classes(yr_amd_scanner* s, uint32_t classes) {
       (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
     return YR_AMD_INVALID_ARGUMENT;
   s->match_classes = classes;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scanner_set_hex_wide(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->hex_wide = enable != 0;
   return YR_AMD_SUCCESS;
 }
 
