@@ -591,7 +591,8 @@ int yr_amd_scan_block_matches(
  * calls (yr_amd_match_batch_device, yr_amd_scan_batch_matches) ignore this
  * setting: they have one of their own, yr_amd_scanner_set_batch_match_classes
  * below, and settle literal strings only until that one says otherwise.  The
- * batch calls never read yr_amd_scanner_set_hex_wide either.
+ * batch calls never read yr_amd_scanner_set_hex_wide either: their wave-wide
+ * path has a setting of its own, yr_amd_scanner_set_batch_hex_wide below.
  *
  * yr_amd_scanner_set_hex_wide(1): a record whose set leaves the 64-position
  * window, or comes within reach of YR_RE_SCAN_LIMIT, is measured by a wave-wide
@@ -867,6 +868,37 @@ int yr_amd_scan_batch_matches(
  * what it launches without this setting.
  */
 int yr_amd_scanner_set_batch_match_classes(yr_amd_scanner* scanner, uint32_t classes);
+
+/*
+ * The batch's wave-wide path.  0 (default): a final hex record of a batch
+ * whose bytes_matched set leaves the 64-position window stays in the rest,
+ * and the batch stage launches exactly what it launches without this setting.
+ * 1: such records are queued on the device with their buffers and measured one
+ * wave each, as yr_amd_scanner_set_hex_wide does for a single block.  Read
+ * only by the batch match calls (yr_amd_match_batch_device,
+ * yr_amd_scan_batch_matches, and through them gathered batches), and only
+ * when the batch classes include YR_AMD_MATCH_HEX; the single-block calls
+ * never read it, the batch calls still never read yr_amd_scanner_set_hex_wide,
+ * and the set of strings (yr_amd_tables_match_strings) is unchanged.  NULL
+ * scanner or a value other than 0/1: YR_AMD_INVALID_ARGUMENT.
+ *
+ * With the setting on, buffer k of a batch gets exactly what
+ * yr_amd_scan_block_matches(data_k, size_k, bases[k]) returns for that buffer
+ * alone on a scanner with classes LITERAL | HEX and
+ * yr_amd_scanner_set_hex_wide(1): matches keyed by (buffer, string, local
+ * offset), the first record in record order supplying length and pool_index,
+ * one record up to 4097 matches.  A wide record is measured inside its own
+ * buffer -- backwards min(local offset, YR_RE_SCAN_LIMIT) bytes, forwards
+ * min(size_k - local offset, YR_RE_SCAN_LIMIT) -- and no byte of a gap or of a
+ * neighbouring buffer is read.  Only two kinds of record of the classes stay
+ * in the rest: a FORWARD program that runs a jump with max > min from several
+ * live positions (yr_amd_scanner_set_hex_wide's note), and the standing
+ * reasons -- no forward program, nothing found.  A batch buffer is never a
+ * window.  YR_AMD_MATCH_MAX_RECORDS still bounds the matches-to-be, and the
+ * stage still waits twice; should the wide records outgrow the device queue,
+ * the first wait sees it, the queue grows and the measure pass runs again.
+ */
+int yr_amd_scanner_set_batch_hex_wide(yr_amd_scanner* scanner, int enable);
 
 /*
  * ---- Block pipeline ----

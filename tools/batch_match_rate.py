@@ -32,6 +32,20 @@ once; then per batch, measured as above:
         re-verification of those records is not measured;
   (d)   one yr_amd_scan_block_matches with the hex class per buffer on the
         first --sample buffers, wall clock, EXTRAPOLATED by n / sample.
+
+    python tools/batch_match_rate.py --hex-wide [--reps 10] [--out profiles/batch_hex_wide_rates.json]
+
+The batch's wave-wide path (yr_amd_scanner_set_batch_hex_wide), classes
+LITERAL | HEX, 256 MiB cut into the same two workloads, the setting off and on
+alternating in one process, medians of --reps after a warm-up with min..max:
+  - C's planted input under C's tables: nothing is queued, on - off is what the
+    setting costs when idle (to be read against the off leg's own spread);
+  - zeros with the hexwide fixture's `back` plant ({ B5 [0-100] B1 B2 B3 B4 },
+    101 matches) once per buffer under the fixture's tables: on - off per wide
+    record;
+  - what a caller had for the second input before: one yr_amd_scan_block_matches
+    with yr_amd_scanner_set_hex_wide(1) per buffer on the first --sample
+    buffers, wall clock, EXTRAPOLATED by n / sample.
 """
 import argparse
 import ctypes
@@ -154,6 +168,106 @@ def hex_leg(a):
             f.write("\n")
 
 
+def hex_wide_leg(a):
+    import numpy as np
+    import torch
+    import yara_amd
+    from yara_amd import _lib
+    sys.path[:0] = [os.path.join(REPO, "tests", "golden")]
+    import gen_rules
+    import oracle
+    import planted
+    L = _lib.lib()
+    stream = torch.cuda.Stream()
+    BOTH = yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX
+    stat = lambda v: {"median": round(statistics.median(v), 4), "min": round(min(v), 4),   # noqa: E731
+                      "max": round(max(v), 4)}
+    golden = os.path.join(REPO, "tests", "golden")
+    total = (256 << 20) // a.scale
+    out = {"bytes": total, "reps": a.reps, "sample": a.sample, "runs": []}
+    for name, path in (("C planted", os.path.join(golden, "tables", "C.npz")),
+                       ("back plant per buffer", os.path.join(golden, "hexwide", "tables.npz"))):
+        t = yara_amd.Tables.from_npz(path, strings=True)
+        for n, size in WORKLOADS:
+            if a.buffers and n != a.buffers:
+                continue
+            n = total // size
+            if name == "C planted":
+                host = planted.planted_buffer(oracle.xorshift, gen_rules.gen("C"), total, 3)
+            else:   # B5 at every depth 1..101 before the atom, as the fixture's `back` plant
+                host = np.zeros((n, size), np.uint8)
+                host[:, 256 - 101:256] = 0xB5
+                host[:, 256:260] = (0xB1, 0xB2, 0xB3, 0xB4)
+                host = host.reshape(-1)
+            buf = torch.empty(total + 16, dtype=torch.uint8, device="cuda")
+            buf[:total] = torch.from_numpy(host).cuda()
+            torch.cuda.synchronize()
+            sizes = np.full(n, size, np.uint64)
+            starts = np.arange(n, dtype=np.uint64) * np.uint64(size)
+            sc = yara_amd.Scanner(t, stream=stream.cuda_stream)
+            sc.set_batch_match_classes(BOTH)
+            sc.scan_batch_device(buf.data_ptr(), total, starts, sizes)
+            sc.batch_result()
+            p1, p2 = ctypes.c_void_p(), ctypes.c_void_p()
+            o1, o2 = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+
+            def stage(wide):   # (ms, matches, rest): the device call alone
+                sc.set_batch_hex_wide(wide)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                _lib.check("yr_amd_match_batch_device", L.yr_amd_match_batch_device(
+                    sc._h, None, ctypes.byref(p1), ctypes.byref(o1), ctypes.byref(p2), ctypes.byref(o2)))
+                e1.record(stream)
+                e1.synchronize()
+                return e0.elapsed_time(e1), int(o1[n]), int(o2[n])
+
+            for _ in range(2):   # warm-up: buffers and the queue grown, clocks up
+                stage(False)
+                stage(True)
+            ms, count = {False: [], True: []}, {}
+            for _ in range(a.reps):   # alternating
+                for wide in (False, True):
+                    v, m, r = stage(wide)
+                    ms[wide].append(v)
+                    count[wide] = (m, r)
+            med = statistics.median
+            wide_records = count[False][1] - count[True][1]
+            run = {"input": name, "buffers": n, "buffer_bytes": size,
+                   "off": {"matches": count[False][0], "rest": count[False][1], "ms": stat(ms[False])},
+                   "on": {"matches": count[True][0], "rest": count[True][1], "ms": stat(ms[True])},
+                   "on_minus_off_ms": round(med(ms[True]) - med(ms[False]), 4),
+                   "wide_records": wide_records}
+            if wide_records:
+                run["us_per_wide_record"] = round(1e3 * run["on_minus_off_ms"] / wide_records, 4)
+                k = min(a.sample, n)   # the path before: a single-block wide call per buffer
+                ptrs = [ctypes.cast(host.ctypes.data + j * size, _lib._u8p) for j in range(k)]
+                pm, pr = ctypes.POINTER(_lib.MatchRec)(), ctypes.POINTER(_lib.VerifyRec)()
+                nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+                one = yara_amd.Scanner(t)
+                one.set_match_classes(BOTH)
+                one.set_hex_wide(True)
+                for warm in (True, False):
+                    t0 = time.perf_counter()
+                    for p in ptrs[:8] if warm else ptrs:
+                        rc = L.yr_amd_scan_block_matches(one._h, p, size, 0, ctypes.byref(pm),
+                                                         ctypes.byref(nm), ctypes.byref(pr), ctypes.byref(nr))
+                        assert rc == 0
+                    sample_ms = (time.perf_counter() - t0) * 1e3
+                one.close()
+                run.update({"singles_sample": k, "singles_sample_ms": round(sample_ms, 3),
+                            "singles_extrapolated_ms": round(sample_ms * n / k, 1),
+                            "singles_is": "extrapolated from the sample by buffers / sample; "
+                                          "includes the scans"})
+            out["runs"].append(run)
+            print(json.dumps(run), flush=True)
+            sc.close()
+            del buf
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="C,short")
@@ -164,7 +278,11 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--hex", action="store_true",
                     help="the batch's hex class on config C's planted input instead of the sets")
+    ap.add_argument("--hex-wide", action="store_true",
+                    help="the batch's wave-wide path, off against on (see above)")
     a = ap.parse_args()
+    if a.hex_wide:
+        return hex_wide_leg(a)
     if a.hex:
         return hex_leg(a)
     import numpy as np

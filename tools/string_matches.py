@@ -35,13 +35,13 @@ than 64 positions).  Several files go through batches as without --hex
 (yr_amd_scanner_set_batch_match_classes): only the files above BLOCK bytes take
 the block path.
 
---hex-wide: --hex, and on the block path (one file, or a file above BLOCK
-bytes) the wave-wide path too (yr_amd_scanner_set_hex_wide): hex calls whose
+--hex-wide: --hex, and the wave-wide path too, on the block path (one file, or
+a file above BLOCK bytes; yr_amd_scanner_set_hex_wide) and in the batches
+several files go through (yr_amd_scanner_set_batch_hex_wide): hex calls whose
 jumps span more than 64 positions are measured as well, whatever the jumps'
-width.  What is left of them are forward programs that run a jump from several
-positions at once, whose match length the reference takes from its list's
-order.  Batches do not read the setting: files that go through them are
-settled as with --hex.
+width, every file's inside the file.  What is left of them are forward programs
+that run a jump from several positions at once, whose match length the
+reference takes from its list's order.
 """
 import gzip
 import os
@@ -106,6 +106,7 @@ def main():
         sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
         sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
     sc.set_hex_wide(hex_wide)
+    sc.set_batch_hex_wide(hex_wide)
     paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))

@@ -271,6 +271,7 @@ class Scanner:
         self._classes = MATCH_LITERAL   # set_match_classes
         self._batch_classes = MATCH_LITERAL   # set_batch_match_classes
         self._hex_wide = False   # set_hex_wide
+        self._batch_hex_wide = False   # set_batch_hex_wide
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -349,7 +350,7 @@ class Scanner:
         """The wave-wide path of the hex class (yr_amd_scanner_set_hex_wide): a
         record whose position set leaves the 64-position window is measured
         too.  Read only while the classes include MATCH_HEX; the batch calls
-        never read it."""
+        never read it (theirs is set_batch_hex_wide)."""
         _lib.check("yr_amd_scanner_set_hex_wide",
                    _lib.lib().yr_amd_scanner_set_hex_wide(self._h, int(enable)))
         self._hex_wide = bool(enable)
@@ -382,16 +383,34 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_batch_match_classes(self._h, classes))
         self._batch_classes = classes
 
-    def _with_batch_hex(self, hex, call):
-        # _with_hex for the batch calls' setting
-        was = self._batch_classes
+    def set_batch_hex_wide(self, enable: bool):
+        """The wave-wide path of the BATCH match stage
+        (yr_amd_scanner_set_batch_hex_wide): a record whose position set leaves
+        the 64-position window is measured too, inside its own buffer.  Read
+        only by the batch calls and only while the batch classes include
+        MATCH_HEX; the single-block calls never read it."""
+        _lib.check("yr_amd_scanner_set_batch_hex_wide",
+                   _lib.lib().yr_amd_scanner_set_batch_hex_wide(self._h, int(enable)))
+        self._batch_hex_wide = bool(enable)
+
+    def _with_batch_hex(self, hex, call, wide=False):
+        # _with_hex for the batch calls' settings
+        was, was_wide = self._batch_classes, self._batch_hex_wide
         if not hex or (was & MATCH_HEX):
-            return call()
-        self.set_batch_match_classes(was | MATCH_HEX)
+            hex = False
+        if not wide or was_wide:
+            wide = False
+        if hex:
+            self.set_batch_match_classes(was | MATCH_HEX)
+        if wide:
+            self.set_batch_hex_wide(True)
         try:
             return call()
         finally:
-            self.set_batch_match_classes(was)
+            if wide:
+                self.set_batch_hex_wide(False)
+            if hex:
+                self.set_batch_match_classes(was)
 
     def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
@@ -583,7 +602,7 @@ class Scanner:
         return self.verify_batch_device(bases)
 
     # -- final matches of a batch ------------------------------------------------
-    def match_batch_device(self, bases=None, hex: bool = False):
+    def match_batch_device(self, bases=None, hex: bool = False, wide: bool = False):
         """(matches, match_off, rest, rest_off) of the last completed batch scan
         (yr_amd_match_batch_device), copied to the host: buffer k's
         ``matches[match_off[k]:match_off[k + 1]]`` and
@@ -592,8 +611,10 @@ class Scanner:
         settles the final hex strings too for this call, as
         ``string_matches(hex=True)`` does for the buffer alone; ``hex=False``
         leaves the scanner's batch classes (set_batch_match_classes) as they
-        are."""
-        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases))
+        are.  ``wide=True`` turns the batch's wave-wide path on for this call
+        (set_batch_hex_wide), as ``string_matches(hex=True, wide=True)`` does
+        for the buffer alone: by itself it does nothing."""
+        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide)
 
     def _match_batch_device(self, bases):
         from ._hip import memcpy
@@ -615,12 +636,12 @@ class Scanner:
             memcpy(rest.ctypes.data, pr.value, rest.size * 16, 2)
         return matches, match_off, rest, rest_off
 
-    def batch_string_matches(self, buffers, bases=None, hex: bool = False):
+    def batch_string_matches(self, buffers, bases=None, hex: bool = False, wide: bool = False):
         """(matches, match_off, rest, rest_off) of a list of host buffers
         (yr_amd_scan_batch_matches): buffer k's slices equal
-        ``string_matches(buffers[k], bases[k], hex=hex)``.  One scan, one
-        pre-verification and one match stage for all of them."""
-        return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases))
+        ``string_matches(buffers[k], bases[k], hex=hex, wide=wide)``.  One scan,
+        one pre-verification and one match stage for all of them."""
+        return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases), wide)
 
     def _batch_string_matches(self, buffers, bases):
         bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
@@ -647,7 +668,8 @@ class Scanner:
             ctypes.memmove(rest.ctypes.data, pr, rest.size * 16)
         return matches, match_off, rest, rest_off
 
-    def batch_string_matches_device(self, buffers, bases=None, hex: bool = False):
+    def batch_string_matches_device(self, buffers, bases=None, hex: bool = False,
+                                    wide: bool = False):
         """batch_string_matches for buffers in device memory (see
         batch_candidates_device), through the gather call."""
         ptrs, sizes = _device_buffers(buffers)
@@ -655,7 +677,7 @@ class Scanner:
             raise ValueError("one base per buffer")
         self.scan_batch_gather_device(ptrs, sizes)
         self.batch_result()
-        return self.match_batch_device(bases, hex=hex)
+        return self.match_batch_device(bases, hex=hex, wide=wide)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

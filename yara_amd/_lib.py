@@ -169,6 +169,7 @@ PROTOTYPES = {
     "yr_amd_scanner_set_match_classes": (_int, [_vp, ctypes.c_uint32]),
     "yr_amd_scanner_set_batch_match_classes": (_int, [_vp, ctypes.c_uint32]),
     "yr_amd_scanner_set_hex_wide": (_int, [_vp, _int]),
+    "yr_amd_scanner_set_batch_hex_wide": (_int, [_vp, _int]),
     "yr_amd_tables_match_strings": (_int, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
 }
 

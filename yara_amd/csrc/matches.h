@@ -237,4 +237,33 @@ hipError_t launch_hex_wide_measure(const HexWideParams& w, uint32_t waves, hipSt
 // launch_hex_expand by istart, then the wide records' items, one wave each.
 hipError_t launch_hex_wide_expand(const HexWideParams& w, uint32_t waves, hipStream_t s);
 
+// ---- The batch's wave-wide path (yr_amd_scanner_set_batch_hex_wide) ----
+// BatchHexParams and HexWideParams at once.  A queue entry is
+// a pair: the record in queue[slot], its buffer in qbuf[slot] -- the measure
+// pass has searched rec_off for it already, and the wide wave takes its bounds
+// [arena + starts[k], + sizes[k]) from there.  A record can be kReScanLimit + 1
+// items, so the items' CSR is read from icount / istart, not from the sets'
+// masks.  The recount and both expansion kernels are the single-block ones:
+// they read none of w.h.m.data / size / win_*, and the queue's first array is
+// theirs as it is.  The sort, the unique pass and match_off go through
+// BatchHexParams (h = w.h) unchanged.
+// A struct of its own: HexWideParams and BatchHexParams are kernel arguments
+// of the kernels above, which stay what they are.
+struct BatchHexWideParams {
+  HexWideParams w;              // w.h.m.data = the arena; size, win_lo, win_hi unused
+  const uint64_t* starts;       // [nbuf] the buffers in the arena
+  const uint64_t* sizes;        // [nbuf]
+  const uint64_t* rec_off;      // [nbuf + 1] CSR of w.h.m.recs
+  uint32_t nbuf;
+  uint32_t* buf;                // [w.h.m.n] by record: its buffer
+  uint32_t* qbuf;               // [w.qcap] by queue slot: the queued record's buffer
+  uint64_t* item_off;           // [nbuf + 1] CSR of the items
+};
+
+// launch_hex_wide_measure for a batch: every record, narrow or wide, measured
+// in its own buffer, + buf.
+hipError_t launch_batch_hex_wide_measure(const BatchHexWideParams& p, uint32_t waves, hipStream_t s);
+// item_off from the scanned item counts (iblock_off / ichunk_off) and istart.
+hipError_t launch_batch_hex_wide_offsets(const BatchHexWideParams& p, hipStream_t s);
+
 }  // namespace yamd

@@ -34,7 +34,9 @@
 // its CSR over the items: the batch_hex_* kernels (BatchHexParams, 18.3).
 // With yr_amd_scanner_set_hex_wide the records whose set leaves hex_run's 64
 // positions are queued and measured one WAVE each, the whole 4096-position
-// set across the lanes: the hex_wide_* kernels (HexWideParams, 18.4).
+// set across the lanes: the hex_wide_* kernels (HexWideParams, 18.4).  A batch
+// has that path too (yr_amd_scanner_set_batch_hex_wide), each record measured
+// inside its own buffer: the batch_hex_wide_* kernels (BatchHexWideParams, 18.5).
 //
 // The comparisons are restated here rather than shared with verify.hip: that
 // file's kernels stay byte for byte what they were (their register budgets are
@@ -1067,62 +1069,71 @@ __device__ int hex_wide_program(const uint8_t* code, uint32_t len, uint8_t* code
   return hex_wide_run(GlobalCode{code}, len, in, maxb, backwards, w, top);
 }
 
+// One queued record, measured by the calling WAVE in the block [data, data +
+// size), loads bounded by [lo, hi).  hex_call's two runs: F = the lowest
+// position of the forward set, the backward set to wsets.  A match overwrites
+// what the queue kernel left of the record: its key (the string in place of
+// n_strings), F, the item count, and the set's mark (mask 0, pad 1).  Anything
+// else leaves the record in the rest.
+__device__ __forceinline__ void hex_wide_record(const HexWideParams& q, uint32_t r, uint32_t slot,
+                                                const uint8_t* data, uint64_t size,
+                                                const uint8_t* lo, const uint8_t* hi, uint8_t* slice,
+                                                uint8_t* codebuf) {
+  const MatchParams& p = q.h.m;
+  const uint32_t lane = threadIdx.x & 63u;
+  const VerifyRec rec = p.recs[r];
+  const DevRe re = p.pool[rec.pool_index].re;
+  const uint64_t offset = rec.offset;
+  const uint8_t* d = data + offset;
+  WideInput in;
+  uint64_t w;
+  bool top;
+  int maxb = (int)min<uint64_t>(size - offset, (uint64_t)kReScanLimit);
+  in.open(slice, d, maxb, false, lo, hi);
+  int v = hex_wide_program(q.h.re_code + re.fwd_off, re.fwd_len, codebuf, in, maxb, false, w, top);
+  if (v != kHexMatch) return;
+  const uint64_t ends = __ballot(w != 0);
+  uint32_t F = kWideTop;   // (top alone)
+  if (ends != 0) {
+    const int first = __builtin_ctzll(ends);
+    F = 64u * first + (uint32_t)__builtin_ctzll(shfl64(w, first) | 1ull << 63);
+  }
+  uint32_t items = 1;
+  w = lane == 0 ? 1ull : 0ull;   // (no backward program: {0})
+  top = false;
+  if (re.bwd_len == 0) {
+    if (F == 0) return;
+  } else {
+    maxb = (int)min<uint64_t>(offset, (uint64_t)kReScanLimit);
+    in.open(slice, d, maxb, true, lo, hi);
+    v = hex_wide_program(q.h.re_code + re.bwd_off, re.bwd_len, codebuf, in, maxb, true, w, top);
+    if (v != kHexMatch) return;
+    items = (uint32_t)__shfl((int)wave_prefix((uint32_t)__popcll(w)), 63, 64) + (top ? 1u : 0u);
+  }
+  uint64_t* ws = q.wsets + (uint64_t)slot * kWideWords;
+  ws[lane] = w;
+  if (lane == 0) {
+    ws[kWideWords - 1] = top ? 1ull : 0ull;
+    p.keys[r] = (uint64_t)p.pool_string[rec.pool_index] << 32 | (offset & 0xFFFFFFFFull);
+    p.meas[r] = MatchMeasure{F, 0u};
+    q.h.sets[r] = HexSet{0ull, 0u, 1u};
+    q.icount[r] = items;
+  }
+}
+
 // One WAVE per queued record, the waves of a fixed grid striding over the
-// queue.  hex_call's two runs: F = the lowest position of the forward set, the
-// backward set to wsets.  A match overwrites what hex_measure_queue_kernel
-// left of the record: its key (the string in place of n_strings), F, the item
-// count, and the set's mark (mask 0, pad 1).  Anything else leaves the record
-// in the rest.  measure_hex's window test lies behind the record already;
-// [win_lo, win_hi) bounds every load.
+// queue.  measure_hex's window test lies behind the record already; [win_lo,
+// win_hi) bounds every load.
 __global__ __launch_bounds__(256) void hex_wide_measure_kernel(HexWideParams q) {
   __shared__ __attribute__((aligned(16))) uint8_t slices[4][kWideSlice];
   __shared__ __attribute__((aligned(16))) uint8_t codes[4][kWideCode];
   const MatchParams& p = q.h.m;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t wave = threadIdx.x >> 6;
   const uint32_t n = min(*q.qlen, q.qcap);
   const uint8_t* lo = p.data + p.win_lo;
   const uint8_t* hi = p.data + p.win_hi;
-  for (uint32_t slot = blockIdx.x * 4 + wave; slot < n; slot += gridDim.x * 4) {
-    const uint32_t r = q.queue[slot];
-    const VerifyRec rec = p.recs[r];
-    const DevRe re = p.pool[rec.pool_index].re;
-    const uint64_t offset = rec.offset;
-    const uint8_t* d = p.data + offset;
-    WideInput in;
-    uint64_t w;
-    bool top;
-    int maxb = (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit);
-    in.open(slices[wave], d, maxb, false, lo, hi);
-    int v = hex_wide_program(q.h.re_code + re.fwd_off, re.fwd_len, codes[wave], in, maxb, false, w, top);
-    if (v != kHexMatch) continue;
-    const uint64_t ends = __ballot(w != 0);
-    uint32_t F = kWideTop;   // (top alone)
-    if (ends != 0) {
-      const int first = __builtin_ctzll(ends);
-      F = 64u * first + (uint32_t)__builtin_ctzll(shfl64(w, first) | 1ull << 63);
-    }
-    uint32_t items = 1;
-    w = lane == 0 ? 1ull : 0ull;   // (no backward program: {0})
-    top = false;
-    if (re.bwd_len == 0) {
-      if (F == 0) continue;
-    } else {
-      maxb = (int)min<uint64_t>(offset, (uint64_t)kReScanLimit);
-      in.open(slices[wave], d, maxb, true, lo, hi);
-      v = hex_wide_program(q.h.re_code + re.bwd_off, re.bwd_len, codes[wave], in, maxb, true, w, top);
-      if (v != kHexMatch) continue;
-      items = (uint32_t)__shfl((int)wave_prefix((uint32_t)__popcll(w)), 63, 64) + (top ? 1u : 0u);
-    }
-    uint64_t* ws = q.wsets + (uint64_t)slot * kWideWords;
-    ws[lane] = w;
-    if (lane == 0) {
-      ws[kWideWords - 1] = top ? 1ull : 0ull;
-      p.keys[r] = (uint64_t)p.pool_string[rec.pool_index] << 32 | (offset & 0xFFFFFFFFull);
-      p.meas[r] = MatchMeasure{F, 0u};
-      q.h.sets[r] = HexSet{0ull, 0u, 1u};
-      q.icount[r] = items;
-    }
-  }
+  for (uint32_t slot = blockIdx.x * 4 + wave; slot < n; slot += gridDim.x * 4)
+    hex_wide_record(q, q.queue[slot], slot, p.data, p.size, lo, hi, slices[wave], codes[wave]);
 }
 
 // The per-wave counts of hex_measure_kernel, from the per-record arrays once
@@ -1196,6 +1207,112 @@ __global__ __launch_bounds__(256) void hex_wide_expand_kernel(HexWideParams w) {
       q.iindex[start + incl] = r;
     }
   }
+}
+
+// ---- The batch's wave-wide path (matches.h BatchHexWideParams) ----
+
+// batch_hex_measure_kernel's twin with the queue (as hex_measure_queue_kernel
+// is hex_measure_kernel's): the record's buffer is the whole block of both
+// runs, a record given up on for width is appended with its buffer -- the
+// binary search over rec_off is done once, here.
+__global__ __launch_bounds__(256) void batch_hex_measure_queue_kernel(BatchHexWideParams b) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const HexWideParams& w = b.w;
+  const MatchParams& p = w.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool wide = false;
+  uint32_t lo = 0;
+  if (r < p.n) {
+    uint32_t hi = b.nbuf;   // rec_off[lo] <= r < rec_off[hi]  (rec_off[nbuf] == n)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (b.rec_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    HexMatchParams q = w.h;
+    q.m.data = p.data + b.starts[lo];
+    q.m.size = b.sizes[lo];
+    q.m.win_lo = 0;
+    q.m.win_hi = q.m.size;
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      const int v = measure_hex<true>(q, e, rec.offset, buf, m, set);
+      is_match = v == kHexMatch;
+      wide = v == kHexWide;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(q.m, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? p.pool_string[rec.pool_index] : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    w.h.sets[r] = set;
+    b.buf[r] = lo;
+    w.icount[r] = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  const uint64_t qmask = __ballot(wide);
+  if (qmask != 0) {   // (wave-uniform)
+    uint32_t at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(w.qlen, (uint32_t)__popcll(qmask));
+    at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(qmask);
+    if (wide && at < w.qcap) {
+      w.queue[at] = (uint32_t)r;
+      b.qbuf[at] = lo;
+    }
+  }
+  // (the per-wave counts are hex_wide_recount_kernel's: they include the wide results)
+}
+
+// hex_wide_measure_kernel for a batch: one WAVE per queued record, a fixed grid
+// striding over the queue.  The wave's record and buffer come from the queue
+// entry, the buffer's bounds from starts / sizes through scalar registers (one
+// value for the wave); both runs see the buffer as the whole block -- position
+// 0 at arena + starts[k], max_bytes_matched = min(size_k - local offset, 4096)
+// forwards and min(local offset, 4096) backwards -- and WideInput loads only
+// from [start, start + size): a 16-byte chunk wholly inside in one aligned load
+// (buffer starts are 16-byte aligned in the arena, their ends are not), the
+// bytes of any other chunk that lie inside one by one, no byte of a gap or of a
+// neighbouring buffer.  The record itself is measured by hex_wide_record.
+__global__ __launch_bounds__(256) void batch_hex_wide_measure_kernel(BatchHexWideParams b) {
+  __shared__ __attribute__((aligned(16))) uint8_t slices[4][kWideSlice];
+  __shared__ __attribute__((aligned(16))) uint8_t codes[4][kWideCode];
+  const HexWideParams& q = b.w;
+  const MatchParams& p = q.h.m;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t n = min(*q.qlen, q.qcap);
+  for (uint32_t slot = uniform(blockIdx.x * 4 + wave); slot < n; slot += gridDim.x * 4) {
+    const uint32_t r = uniform(q.queue[slot]), k = uniform(b.qbuf[slot]);
+    if (r >= p.n || k >= b.nbuf) continue;   // (never: what the measure pass appended)
+    const uint8_t* lo = p.data + b.starts[k];
+    const uint64_t size = b.sizes[k];
+    if (p.recs[r].offset >= size) continue;   // (never: measure_hex queues no such record)
+    hex_wide_record(q, r, slot, lo, size, lo, lo + size, slices[wave], codes[wave]);
+  }
+}
+
+// The CSR offsets over items, one lane per k in [0, nbuf], without a loop:
+// item_off[k] = the items of the records below c0 = rec_off[k] = the scanned
+// item count of c0's wave plus, where c0 is not the wave's first record, what
+// the recount left of the record before it: its items' start within the wave
+// and its item count.  (g == groups: the entry past the last wave, the total.)
+__global__ __launch_bounds__(256) void batch_hex_wide_offsets_kernel(BatchHexWideParams b) {
+  const HexWideParams& w = b.w;
+  const MatchParams& p = w.h.m;
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > b.nbuf) return;
+  const uint64_t c0 = b.rec_off[k], g = c0 / kGroup;
+  uint64_t o = w.h.ichunk_off[g / kChunkGroups] + w.h.iblock_off[g];
+  if (c0 % kGroup != 0) {   // (c0 - 1 is a record of the same wave)
+    const uint64_t c = c0 - 1;
+    o += w.istart[c] + ((uint32_t)(p.keys[c] >> 32) == p.n_strings ? 0u : w.icount[c]);
+  }
+  b.item_off[k] = o;
 }
 
 }  // namespace
@@ -1298,6 +1415,25 @@ hipError_t launch_hex_wide_expand(const HexWideParams& w, uint32_t waves, hipStr
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(hex_expand_at_kernel, match_grid(p.m.n), dim3(256), 0, s, w);
   hipLaunchKernelGGL(hex_wide_expand_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_hex_wide_measure(const BatchHexWideParams& p, uint32_t waves, hipStream_t s) {
+  const uint64_t n = p.w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || p.w.qcap == 0 || p.nbuf == 0) return hipErrorInvalidValue;
+  // (a kernel, not a memset: the stage may be recorded into a graph)
+  hipLaunchKernelGGL(hex_wide_clear_kernel, dim3(1), dim3(1), 0, s, p.w);
+  hipLaunchKernelGGL(batch_hex_measure_queue_kernel, match_grid(n), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(batch_hex_wide_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(hex_wide_recount_kernel, match_grid(n), dim3(256), 0, s, p.w);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_hex_wide_offsets(const BatchHexWideParams& p, hipStream_t s) {
+  const uint64_t n = p.w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_hex_wide_offsets_kernel, match_grid((uint64_t)p.nbuf + 1), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

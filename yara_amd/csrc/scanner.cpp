@@ -257,7 +257,13 @@ struct yr_amd_scanner {
   // the wave-wide path of the hex class (yr_amd_scanner_set_hex_wide; matches.h
   // HexWideParams)
   bool hex_wide = false;
-  uint32_t* d_wqueue = nullptr;         // [1 + cap]: the queue's length, the queued records
+  // the batch's own setting (yr_amd_scanner_set_batch_hex_wide; matches.h
+  // BatchHexWideParams): the queue then holds a second array, the records' buffers
+  bool batch_hex_wide = false;
+  // d_wqueue is laid out per call by the driver that uses it, within wqueue_cap words:
+  // single block [1 + cap]: the queue's length, the queued records;
+  // batch [1 + 2 cap]: the length, the queued records, their buffers (qbuf)
+  uint32_t* d_wqueue = nullptr;
   size_t wqueue_cap = 0;
   uint64_t* d_wsets = nullptr;          // [cap * kWideWords] the backward sets by queue slot
   size_t wsets_cap = 0;
@@ -2433,24 +2439,72 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   rp.nbuf = nbuf;
   rp.rest_off = s->d_moff + noff;
   const KeptLists none{{0, 0, 0, 0}};
-  // measure -> the offsets of the rest and of the items -> the rest, its CSR
-  // and the items' CSR; wait
-  HIP_TRY(launch_batch_hex_measure(b, s->stream));
-  HIP_TRY(launch_block_offsets(m.block_off, m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
-  HIP_TRY(launch_block_offsets(b.h.iblock_off, b.h.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
-                               s->stream));
-  HIP_TRY(launch_match_rest(m, s->stream));
-  HIP_TRY(launch_batch_match_offsets(rp, 0, s->stream));
-  HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
-  HIP_TRY(hipMemcpyAsync(s->h_mrest_off.data(), rp.rest_off, noff * sizeof(uint64_t),
-                         hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
+  // The batch's wave-wide path (BatchHexWideParams), as in match_device_hex: the
+  // records given up on for width are queued with their buffers and measured one
+  // wave each, the queue's length not waited for; should it pass the capacity,
+  // the wait below sees that and the pass runs again with a larger queue.
+  const bool wide = s->batch_hex_wide;
+  const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
+  BatchHexWideParams bw{};
+  uint64_t queued = 0;
+  // (the inverse of the layout [1 + 2 qcap]: a capacity that holds the queue reallocates nothing)
+  for (size_t qcap = std::max<size_t>((s->wqueue_cap > 0 ? s->wqueue_cap - 1 : 0) / 2, 256);;
+       qcap = std::max<size_t>(queued, 2 * qcap)) {
+    if (wide) {
+      qcap = std::min<size_t>(qcap, kMatchMaxRecords);
+      r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + 2 * qcap);   // the length, the records, their buffers
+      if (!r) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
+      if (!r) r = grow_geo(s->d_wcount, s->wcount_cap, 2 * n);
+      if (r) return r;
+      bw.w.h = b.h;
+      bw.w.qlen = s->d_wqueue;
+      bw.w.queue = s->d_wqueue + 1;
+      bw.w.qcap = (uint32_t)qcap;
+      bw.w.qlen_out = s->d_mhsum + 4;
+      bw.w.wsets = s->d_wsets;
+      bw.w.icount = s->d_wcount;
+      bw.w.istart = s->d_wcount + n;
+      bw.starts = b.starts;
+      bw.sizes = b.sizes;
+      bw.rec_off = b.rec_off;
+      bw.nbuf = nbuf;
+      bw.buf = b.buf;
+      bw.qbuf = s->d_wqueue + 1 + qcap;
+      bw.item_off = b.item_off;
+    }
+    // measure -> the offsets of the rest and of the items -> the rest, its CSR
+    // and the items' CSR; wait
+    if (wide)
+      HIP_TRY(launch_batch_hex_wide_measure(bw, wide_waves, s->stream));
+    else
+      HIP_TRY(launch_batch_hex_measure(b, s->stream));
+    HIP_TRY(launch_block_offsets(m.block_off, m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
+    HIP_TRY(launch_block_offsets(b.h.iblock_off, b.h.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
+                                 s->stream));
+    HIP_TRY(launch_match_rest(m, s->stream));
+    HIP_TRY(launch_batch_match_offsets(rp, 0, s->stream));
+    if (wide)
+      HIP_TRY(launch_batch_hex_wide_offsets(bw, s->stream));
+    else
+      HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->h_mrest_off.data(), rp.rest_off, noff * sizeof(uint64_t),
+                           hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    queued = wide ? s->h_msum[4] : 0;
+    if (queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    if (!wide || queued <= bw.w.qcap) break;
+  }
   *nr = s->h_msum[0];
   const uint64_t items = s->h_msum[3];
   *ni = items;
   *nm = 0;
-  if (*nr > n || items > 64 * (n - *nr) || s->h_mrest_off[nbuf] != *nr)
+  // (a record of the wave-wide path is up to YR_RE_SCAN_LIMIT + 1 items)
+  if (*nr > n || items > (wide ? (uint64_t)kReScanLimit + 1 : 64) * (n - *nr) ||
+      s->h_mrest_off[nbuf] != *nr)
     return YR_AMD_INTERNAL_FATAL_ERROR;
+  if (debug_level() >= 1 && wide)
+    fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_batch_device()\n",
+            (unsigned long long)n, (unsigned long long)queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   if (items == 0) return YR_AMD_SUCCESS;
   r = ensure_match_workspace(s, items);
@@ -2472,7 +2526,12 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort by (buffer, string, offset); distinct (buffer, key) -> their
   // offsets -> the matches and their CSR; wait
-  HIP_TRY(launch_hex_expand(b.h, s->stream));
+  if (wide) {
+    bw.w.h = b.h;
+    HIP_TRY(launch_hex_wide_expand(bw.w, wide_waves, s->stream));
+  } else {
+    HIP_TRY(launch_hex_expand(b.h, s->stream));
+  }
   int sorted = 0;
   HIP_TRY(batch_match_sort(keys, index, items, lo_bits, hi_bits, b.buf, nbuf, s->d_mhist,
                            s->d_mhchunk, s->d_mhsum + 2, s->stream, &sorted));
@@ -2498,6 +2557,12 @@ int yr_amd_scanner_set_batch_match_classes(yr_amd_scanner* s, uint32_t classes) 
       (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
     return YR_AMD_INVALID_ARGUMENT;
   s->batch_match_classes = classes;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scanner_set_batch_hex_wide(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->batch_hex_wide = enable != 0;
   return YR_AMD_SUCCESS;
 }
 
