@@ -624,6 +624,78 @@ int yr_amd_tables_match_strings(
     uint32_t n_strings);
 
 /*
+ * ---- Chained strings: hex strings split at a wide jump ----
+ *
+ * libyara's compiler splits a hex string at every jump wider than
+ * YR_STRING_CHAINING_THRESHOLD (200) into a chain of strings S0 <- S1 <- ...,
+ * each carrying STRING_FLAGS_CHAIN_PART (0x2000), the last one CHAIN_TAIL
+ * (0x4000); _yr_scan_verify_chained_string_match (scan.c:406-632) assembles
+ * the parts' matches into matches of the head S0.  No part is a string of a
+ * match class, so without this section every call of a chain stays in the rest.
+ *
+ * yr_amd_tables_set_chains attaches the links: chained_to[k] is the index of
+ * YR_STRING.chained_to (0xFFFFFFFF: none), the gaps are chain_gap_min / _max.
+ * Once per tables, device or host-only, after the string records or flags;
+ * n_strings is the tables' string count.  YR_AMD_INVALID_ARGUMENT for: an index
+ * out of range; a string chained to itself, or a cycle; a negative gap;
+ * gap_max < gap_min; a link on or to a string without CHAIN_PART; two strings
+ * chained to one; CHAIN_TAIL anywhere but on the string that has a link and is
+ * the target of none.  yr_amd_tables_load_yarc attaches them itself (a
+ * chained_to reference that is not a string record makes the file invalid).
+ *
+ * A chain is SETTLED with `classes` when every one of its strings, the two
+ * chain bits masked off its flags, is a string of the classes (a literal part
+ * with YR_AMD_MATCH_LITERAL, a part with wildcards with YR_AMD_MATCH_HEX; a
+ * regexp's parts never), no part carries STRING_FLAGS_XOR (a chain's match has
+ * xor_key 0: the parts' keys are not kept; compiled rules have no such part) and
+ * it has at most 64 parts.
+ * yr_amd_tables_chain_strings: out[k] = 1 iff string k is part of a settled
+ * chain.  Host code; it refuses what yr_amd_tables_match_strings refuses, and
+ * tables without chain records.
+ *
+ * yr_amd_scanner_set_chains(1): yr_amd_match_device and
+ * yr_amd_scan_block_matches (the batch calls never read it) also report the
+ * settled chains' matches, exactly libyara's lists:
+ *   - the events of a chain are its parts' kept records in record order, each
+ *     measured as a final string of its class is (a hex part by the
+ *     64-position sets: offset - B, length B + F);
+ *   - they are replayed through scan.c:406-632 as it stands -- the unconfirmed
+ *     lists, the pruning, the chain lengths, the confirm sweep -- and every
+ *     confirmed head is a match {head string, offset, tail offset - offset +
+ *     tail length, xor_key 0, pool_index of the head's record}, in the same
+ *     ascending (string, offset) list as all others, the first confirmation of
+ *     an offset kept;
+ *   - a chain is DIRTY when one of its records is not exactly one event (a hex
+ *     part with more than one backward result, a set that leaves the 64
+ *     positions, no forward program): all its records stay in the rest, in
+ *     place, and it yields no match.  A record that measures to nothing is no
+ *     event and stays in the rest without dirtying the chain;
+ *   - the records of a settled, clean chain that are events are not in the
+ *     rest, whose order is otherwise unchanged.
+ * After a scan that did not cover the whole block ([0, block_size) as window
+ * and as byte range) every chain record stays in the rest: a shard does not see
+ * the other parts.  YR_MAX_STRING_MATCHES and fast mode are host state and not
+ * applied.  With the setting on and no chain records on the tables the two
+ * calls return YR_AMD_INVALID_ARGUMENT; with it off they launch what they
+ * launched before.  The stage still waits twice (with the literal class alone
+ * and chains on: twice instead of once) -- the replay is queued ahead of the
+ * first wait, its item count read with the hex items'.
+ * NULL scanner or a value other than 0/1: YR_AMD_INVALID_ARGUMENT.
+ */
+int yr_amd_tables_set_chains(
+    yr_amd_tables* tables,
+    const uint32_t* chained_to,
+    const int32_t* gap_min,
+    const int32_t* gap_max,
+    uint32_t n_strings);
+int yr_amd_tables_chain_strings(
+    const yr_amd_tables* tables,
+    uint32_t classes,
+    uint8_t* out,
+    uint32_t n_strings);
+int yr_amd_scanner_set_chains(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
+
+/*
  * ---- Batched scans: many independent buffers in one launch ----
  *
  * Every call above takes one block and pays its fixed cost -- a scan launch in

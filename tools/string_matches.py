@@ -1,6 +1,6 @@
 """Which literal strings of a compiled rules file match where in a file.
 
-    python tools/string_matches.py [--hex | --hex-wide] RULES.yarc FILE [FILE ...]
+    python tools/string_matches.py [--hex | --hex-wide] [--chains] RULES.yarc FILE [FILE ...]
 
 Prints one "string offset length xor" line per match of a final string
 (include/yara_amd.h: literal, not a chain part, not base64) -- absolute file
@@ -42,6 +42,13 @@ jumps span more than 64 positions are measured as well, whatever the jumps'
 width, every file's inside the file.  What is left of them are forward programs
 that run a jump from several positions at once, whose match length the
 reference takes from its list's order.
+
+--chains: the chained hex strings too (yr_amd_scanner_set_chains): a hex string
+that libyara split at a jump wider than 200 bytes is printed as matches of its
+first part, the chain's head, assembled on the GPU as stock libyara assembles
+them.  The parts are settled as the classes settle strings: literal parts
+always, parts with wildcards with --hex.  Chains are per block, and the batch
+calls do not settle them: with --chains every file takes the block path.
 """
 import gzip
 import os
@@ -91,8 +98,9 @@ def arenas(sizes):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--hex", "--hex-wide")]
-    hex_class = len(argv) != len(sys.argv) - 1
+    argv = [a for a in sys.argv[1:] if a not in ("--hex", "--hex-wide", "--chains")]
+    hex_class = "--hex" in sys.argv[1:] or "--hex-wide" in sys.argv[1:]
+    chains = "--chains" in sys.argv[1:]
     hex_wide = "--hex-wide" in sys.argv[1:]
     if len(argv) < 2:
         sys.exit(__doc__)
@@ -107,6 +115,7 @@ def main():
         sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
     sc.set_hex_wide(hex_wide)
     sc.set_batch_hex_wide(hex_wide)
+    sc.set_chains(chains)
     paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))
@@ -116,7 +125,7 @@ def main():
         return
     sizes = [os.path.getsize(p) for p in paths]
     per, left = [None] * len(paths), 0
-    for group in arenas(sizes):
+    for group in ([] if chains else arenas(sizes)):
         try:
             m, mo, rest, _ = sc.batch_string_matches(
                 [np.fromfile(paths[k], dtype=np.uint8) for k in group])
@@ -128,7 +137,7 @@ def main():
             per[k] = m[int(mo[j]):int(mo[j + 1])]
         left += len(rest)
     for k, p in enumerate(paths):
-        if per[k] is None:   # larger than BLOCK
+        if per[k] is None:   # larger than BLOCK, or --chains
             per[k], n = block_path(sc, np.fromfile(p, dtype=np.uint8))
             left += n
         for r in per[k]:

@@ -130,7 +130,31 @@ class Tables:
             if regex and "re_kind" in z:
                 fl = np.where(z["re_kind"] != 0, z["re_fwd_len"], 0)
                 t.set_re_code(z["re_fwd_off"], fl, z["re_bwd_off"], z["re_bwd_len"], z["re_code"])
+        if strings and all(k in z for k in ("str_chained_to", "str_gap_min", "str_gap_max")):
+            t.set_chains(z["str_chained_to"], z["str_gap_min"], z["str_gap_max"])
         return t
+
+    def set_chains(self, chained_to, gap_min, gap_max):
+        """Attach the chain links of the strings (yr_amd_tables_set_chains):
+        ``chained_to[k]`` the index of YR_STRING.chained_to (0xFFFFFFFF: none),
+        the gaps chain_gap_min / chain_gap_max."""
+        to = _arr(chained_to, np.uint32).reshape(-1)
+        lo, hi = (_arr(g, np.int32).reshape(-1) for g in (gap_min, gap_max))
+        if not (to.size == lo.size == hi.size):
+            raise ValueError("chain arrays differ in length")
+        _lib.check("yr_amd_tables_set_chains", _lib.lib().yr_amd_tables_set_chains(
+            self._h, to.ctypes.data_as(_lib._u32p) if to.size else None,
+            lo.ctypes.data_as(_lib._i32p) if to.size else None,
+            hi.ctypes.data_as(_lib._i32p) if to.size else None, to.size))
+
+    def chain_strings(self, classes: int = MATCH_LITERAL):
+        """bool[n_strings]: the parts of the chains that ``Scanner.set_chains``
+        settles with these classes (yr_amd_tables_chain_strings)."""
+        n = self.string_count()
+        out = np.zeros(max(n, 1), np.uint8)
+        _lib.check("yr_amd_tables_chain_strings", _lib.lib().yr_amd_tables_chain_strings(
+            self._h, classes, out.ctypes.data_as(_lib._u8p), n))
+        return out[:n].astype(bool)
 
     def set_re_code(self, fwd_off, fwd_len, bwd_off, bwd_len, code):
         """Attach fast-exec RE programs (yr_amd_tables_set_re_code)."""
@@ -272,6 +296,7 @@ class Scanner:
         self._batch_classes = MATCH_LITERAL   # set_batch_match_classes
         self._hex_wide = False   # set_hex_wide
         self._batch_hex_wide = False   # set_batch_hex_wide
+        self._chains = False   # set_chains
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -355,21 +380,37 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_hex_wide(self._h, int(enable)))
         self._hex_wide = bool(enable)
 
-    def _with_hex(self, hex, call, wide=False):
+    def set_chains(self, enable: bool):
+        """Settle chained hex strings too (yr_amd_scanner_set_chains): the
+        matches of the heads of the chains ``Tables.chain_strings`` names, as
+        stock libyara assembles them.  The tables need chain records; the
+        batch calls never read it."""
+        _lib.check("yr_amd_scanner_set_chains",
+                   _lib.lib().yr_amd_scanner_set_chains(self._h, int(enable)))
+        self._chains = bool(enable)
+
+    def _with_hex(self, hex, call, wide=False, chains=False):
         # hex=True: this call with the hex class added (wide=True: and the
-        # wave-wide path on), the scanner's settings restored
+        # wave-wide path on; chains=True: and chained strings settled), the
+        # scanner's settings restored
         was, was_wide = self._classes, self._hex_wide
         if not hex or (was & MATCH_HEX):
             hex = False
         if not wide or was_wide:
             wide = False
+        if not chains or self._chains:
+            chains = False
         if hex:
             self.set_match_classes(was | MATCH_HEX)
         if wide:
             self.set_hex_wide(True)
+        if chains:
+            self.set_chains(True)
         try:
             return call()
         finally:
+            if chains:
+                self.set_chains(False)
             if wide:
                 self.set_hex_wide(False)
             if hex:
@@ -412,7 +453,8 @@ class Scanner:
             if hex:
                 self.set_batch_match_classes(was)
 
-    def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False):
+    def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False,
+                     chains: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
         copied to the host: ``matches`` {offset, string, length, xor_key,
         pool_index}, one per distinct (string, offset) of the final strings
@@ -426,8 +468,10 @@ class Scanner:
         (set_match_classes) as they are.  ``wide=True`` turns the wave-wide
         path of the hex class on for this call (set_hex_wide): by itself it
         implies nothing, it goes with ``hex=True`` or a scanner whose classes
-        hold MATCH_HEX."""
-        return self._with_hex(hex, lambda: self._match_device(data_base), wide)
+        hold MATCH_HEX.  ``chains=True`` settles the chained strings for this
+        call (set_chains): the heads' matches join ``matches``, the events of
+        settled, clean chains leave ``rest``."""
+        return self._with_hex(hex, lambda: self._match_device(data_base), wide, chains)
 
     def _match_device(self, data_base):
         from ._hip import memcpy
@@ -445,12 +489,12 @@ class Scanner:
         return matches, rest
 
     def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False,
-                       wide: bool = False):
+                       wide: bool = False, chains: bool = False):
         """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
         see match_device.  For the final strings ``matches`` is what stock
         libyara's match lists hold after scanning this block alone; the blocks
         of one scan merge with ``merge_matches``."""
-        return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide)
+        return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide, chains)
 
     def _string_matches(self, data, data_base):
         d = _arr(data, np.uint8)

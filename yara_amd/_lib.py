@@ -25,6 +25,7 @@ _u32p = ctypes.POINTER(ctypes.c_uint32)
 _u16p = ctypes.POINTER(ctypes.c_uint16)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
+_i32p = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
 _int = ctypes.c_int
 
@@ -169,6 +170,9 @@ PROTOTYPES = {
     "yr_amd_scanner_set_match_classes": (_int, [_vp, ctypes.c_uint32]),
     "yr_amd_scanner_set_batch_match_classes": (_int, [_vp, ctypes.c_uint32]),
     "yr_amd_scanner_set_hex_wide": (_int, [_vp, _int]),
+    "yr_amd_tables_set_chains": (_int, [_vp, _u32p, _i32p, _i32p, ctypes.c_uint32]),
+    "yr_amd_tables_chain_strings": (_int, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
+    "yr_amd_scanner_set_chains": (_int, [_vp, _int]),
     "yr_amd_scanner_set_batch_hex_wide": (_int, [_vp, _int]),
     "yr_amd_tables_match_strings": (_int, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
 }

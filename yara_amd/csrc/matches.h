@@ -266,4 +266,70 @@ hipError_t launch_batch_hex_wide_measure(const BatchHexWideParams& p, uint32_t w
 // item_off from the scanned item counts (iblock_off / ichunk_off) and istart.
 hipError_t launch_batch_hex_wide_offsets(const BatchHexWideParams& p, hipStream_t s);
 
+// ---- Chained strings (yr_amd_scanner_set_chains; chains.hip) ----
+// libyara splits a hex string at every jump wider than
+// YR_STRING_CHAINING_THRESHOLD into a chain S0 <- S1 <- ... (chained_to links
+// a part to the one before it); _yr_scan_verify_chained_string_match
+// (scan.c:406-632) assembles the parts' matches into the head's.  A chain is
+// SETTLED with the classes when each part, the chain bits masked off, is a
+// string of the classes; its records then become EVENTS, replayed per chain in
+// record order by one wave.
+constexpr uint32_t kStrChainTail = 0x4000;   // STRING_FLAGS_CHAIN_TAIL
+constexpr uint32_t kNoChain = 0xFFFFFFFFu;
+constexpr uint32_t kChainMaxLevels = 64;     // a level's state lives in its lane
+
+// (Not an XOR part: a chain's match carries xor_key 0, the parts' keys are not
+// kept.  The compiler makes chains of hex strings and regexps, which have none.)
+__host__ __device__ inline bool string_settles_in_chain(uint32_t flags, uint32_t classes) {
+  return (flags & kStrXor) == 0 &&
+         string_in_classes(flags & ~(kStrChainPart | kStrChainTail), classes);
+}
+
+// The tables' chain records on the device (yr_amd_tables_set_chains).
+struct ChainTables {
+  const uint32_t* chain_of;     // [n_strings] the string's chain, kNoChain: none
+  const uint32_t* level_of;     // [n_strings] its place in the chain, the head's 0
+  const int32_t* gap_min;       // [n_strings] YR_STRING.chain_gap_min / _max: the distance
+  const int32_t* gap_max;       //   from the end of the part before it
+  const uint32_t* chain_off;    // [n_chains + 1] CSR of chain_strs
+  const uint32_t* chain_strs;   // the chains' strings by level
+  const uint8_t* settled;       // [n_chains] bit (classes >> 1): settled with LITERAL / + HEX
+  uint32_t n_chains;
+};
+
+// m / re_code / classes / sets are the measure pass's (HexMatchParams): the
+// stage runs behind it and rewrites what it wrote for the records it consumes
+// -- key string field n_strings + 1 (neither a match nor the rest), an empty
+// set, the per-wave rest counts in m.block_off.
+struct ChainParams {
+  HexMatchParams h;
+  ChainTables t;
+  uint32_t* rchain;             // [n] by record: its chain if it is an event, else n_chains
+  uint32_t* ev_level;           // [n] by record: the event {level, offset, length}
+  uint32_t* ev_offset;
+  uint32_t* ev_length;
+  uint32_t* dirty;              // [n_chains] some record of the chain is not exactly one event
+  uint64_t* str_off;            // [n_strings + 1] events per string -> offsets within chunks
+  uint64_t* str_chunk;          // [verify_chunks(n_strings * kGroup) + 1]
+  uint64_t* skeys;              // [n] the sort's keys: rchain (values: the record)
+  uint32_t* sindex;
+  const uint64_t* sorted_keys;  // after the stable sort by chain
+  const uint32_t* sorted_index;
+  uint32_t* cbegin;             // [n_chains] the chain's events in the sorted arrays
+  uint32_t* cend;
+  uint32_t* lists;              // [4][n] the unconfirmed lists past the LDS share: offset,
+                                //   length, chain_length, record; string k's at str_off(k)
+  uint64_t* item_keys;          // [n] the confirmed heads: string << 32 | offset
+  uint32_t* item_index;         // [n] the head's record
+  uint32_t* item_count;         // items appended
+};
+
+// Clear; one lane per record: the event or the dirty flag; then, the flags
+// complete, the consumed records marked and the rest recounted + skeys / sindex.
+hipError_t launch_chain_events(const ChainParams& c, hipStream_t s);
+// (str_off scanned, skeys sorted) the chains' bounds, then one wave per chain
+// with events: scan.c:406-632 over its events, the confirmed heads appended as
+// items and their lengths left in m.meas at the head's record.
+hipError_t launch_chain_replay(const ChainParams& c, uint32_t waves, hipStream_t s);
+
 }  // namespace yamd

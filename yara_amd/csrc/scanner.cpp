@@ -120,6 +120,14 @@ struct yr_amd_tables {
   bool has_str_flags = false;         // yr_amd_tables_set_string_flags (host-only tables)
   uint32_t* d_pool_string = nullptr;  // [n_pool] the entries' string indexes (matches.hip)
   uint64_t max_str_bytes = 0;     // max over strings of the bytes a comparison reads
+
+  // chain records (yr_amd_tables_set_chains; matches.h ChainTables): host
+  // copies, and on device tables one allocation that d_chain points into
+  bool has_chains = false;
+  std::vector<uint32_t> h_chain_of, h_chain_strs, h_chain_off;
+  std::vector<uint8_t> h_chain_settled;
+  uint32_t* d_chain_words = nullptr;
+  ChainTables d_chain{};
 };
 
 struct yr_amd_scanner {
@@ -226,7 +234,7 @@ struct yr_amd_scanner {
   size_t mhist_cap = 0;
   uint64_t* d_mhchunk = nullptr;
   size_t mhchunk_cap = 0;
-  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued}
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued, chain items}
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
@@ -269,6 +277,11 @@ struct yr_amd_scanner {
   size_t wsets_cap = 0;
   uint32_t* d_wcount = nullptr;         // [2 * cap]: items by record, their starts within the wave
   size_t wcount_cap = 0;
+  // chained strings (yr_amd_scanner_set_chains; matches.h ChainParams): one
+  // workspace, laid out per call by match_device_hex
+  bool chains = false;
+  uint64_t* d_chain_ws = nullptr;
+  size_t chain_ws_cap = 0;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -469,7 +482,7 @@ int yr_amd_tables_destroy(yr_amd_tables* t) {
   if (t == nullptr) return YR_AMD_SUCCESS;
   for (void* p : {(void*)t->d_filter, (void*)t->d_exact, (void*)t->d_nodes, (void*)t->d_kc, (void*)t->d_pool,
                   (void*)t->d_str_bytes, (void*)t->d_lowercase, (void*)t->d_re_code,
-                  (void*)t->d_pool_string})
+                  (void*)t->d_pool_string, (void*)t->d_chain_words})
     if (p) (void)hipFree(p);
   delete t;
   return YR_AMD_SUCCESS;
@@ -566,7 +579,8 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_mout, (void*)s->d_mblock, (void*)s->d_mchunk, (void*)s->d_mhist,
                   (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff, (void*)s->d_hkeys,
                   (void*)s->d_hmeas, (void*)s->d_hsets, (void*)s->d_hrest, (void*)s->d_hblock,
-                  (void*)s->d_hchunk, (void*)s->d_wqueue, (void*)s->d_wsets, (void*)s->d_wcount})
+                  (void*)s->d_hchunk, (void*)s->d_wqueue, (void*)s->d_wsets, (void*)s->d_wcount,
+                  (void*)s->d_chain_ws})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1746,7 +1760,7 @@ int reallocate(T*& p, size_t need) {
 // two CSR offset arrays too.
 int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (s->h_msum == nullptr) {
-    if (hipHostMalloc((void**)&s->h_msum, 5 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
+    if (hipHostMalloc((void**)&s->h_msum, 6 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
       s->h_msum = nullptr;
       return YR_AMD_INSUFFICIENT_MEMORY;
     }
@@ -1781,11 +1795,16 @@ int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
 
 // The stage with the hex class: records -> items -> matches (matches.h
 // HexMatchParams).  Two waits: the item count sizes the sort's workspace.
+// chains: the records of settled chains become events and these the heads'
+// items (matches.h ChainParams), all of it queued ahead of the first wait --
+// the same two waits.
 int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n, uint64_t* nm,
-                     uint64_t* nr) {
+                     uint64_t* nr, bool chains) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
-  int r = ensure_match_workspace(s, 1);   // (the pinned totals; the items' arrays grow below)
+  // (the pinned totals; the items' arrays grow below.  With chains the events'
+  // sort by chain runs in the items' arrays before the items exist.)
+  int r = ensure_match_workspace(s, chains ? n : 1);
   if (!r) r = grow_geo(s->d_hkeys, s->hkeys_cap, n);
   if (!r) r = grow_geo(s->d_hmeas, s->hmeas_cap, n);
   if (!r) r = grow_geo(s->d_hsets, s->hsets_cap, n);
@@ -1817,6 +1836,36 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   p.iblock_off = s->d_hblock + groups;
   p.ichunk_off = s->d_hchunk + chunks;
   const KeptLists none{{0, 0, 0, 0}};
+  ChainParams c{};
+  const uint32_t n_chains = t->d_chain.n_chains;
+  const uint32_t chain_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
+  int chain_bits = 1;   // the sort key's values: a chain, or n_chains for "no event"
+  if (chains) {
+    while (chain_bits < 32 && (n_chains >> chain_bits) != 0) ++chain_bits;
+    // the workspace: the 64-bit arrays first, then the 32-bit ones
+    const size_t ns = p.m.n_strings, str_chunks = verify_chunks((uint64_t)ns * kGroup) + 1;
+    const size_t words64 = n + (ns + 1) + str_chunks;
+    const size_t words32 = 9 * n + 3 * (size_t)n_chains + 2;
+    r = grow_geo(s->d_chain_ws, s->chain_ws_cap, words64 + (words32 + 1) / 2);
+    if (r) return r;
+    c.t = t->d_chain;
+    c.item_keys = s->d_chain_ws;
+    c.str_off = c.item_keys + n;
+    c.str_chunk = c.str_off + ns + 1;
+    uint32_t* w = reinterpret_cast<uint32_t*>(s->d_chain_ws + words64);
+    c.rchain = w;
+    c.ev_level = w + n;
+    c.ev_offset = w + 2 * n;
+    c.ev_length = w + 3 * n;
+    c.lists = w + 4 * n;
+    c.item_index = w + 8 * n;
+    c.dirty = w + 9 * n;
+    c.cbegin = c.dirty + n_chains;
+    c.cend = c.cbegin + n_chains;
+    c.item_count = c.cend + n_chains;
+    c.skeys = s->d_mkeys;
+    c.sindex = s->d_mindex;
+  }
   // The wave-wide path: the records the lane-per-record measure gives up on for
   // width are queued and measured one wave each, a fixed grid of a few waves per
   // CU striding over the queue -- its length is not waited for.  Should it pass
@@ -1845,19 +1894,42 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
       HIP_TRY(launch_hex_wide_measure(w, wide_waves, s->stream));
     else
       HIP_TRY(launch_hex_measure(p, s->stream));
+    if (chains) {   // the events; their records out of the rest's counts
+      c.h = p;
+      HIP_TRY(launch_chain_events(c, s->stream));
+    }
     HIP_TRY(launch_block_offsets(p.m.block_off, p.m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
     HIP_TRY(launch_block_offsets(p.iblock_off, p.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
                                  s->stream));
     HIP_TRY(launch_match_rest(p.m, s->stream));
+    if (chains) {
+      // the lists' places; the events by chain, in record order; the replay
+      uint64_t* const ckeys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+      uint32_t* const cindex[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+      HIP_TRY(launch_block_offsets(c.str_off, c.str_chunk, (uint64_t)p.m.n_strings * kGroup,
+                                   s->d_mhsum + 2, nullptr, none, s->stream));
+      int csorted = 0;
+      HIP_TRY(match_sort(ckeys, cindex, n, chain_bits, 0, s->d_mhist, s->d_mhchunk, s->d_mhsum + 2,
+                         s->stream, &csorted));
+      c.sorted_keys = ckeys[csorted];
+      c.sorted_index = cindex[csorted];
+      HIP_TRY(launch_chain_replay(c, chain_waves, s->stream));
+      HIP_TRY(hipMemcpyAsync(s->h_msum + 5, c.item_count, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                             s->stream));
+    }
     HIP_TRY(hipStreamSynchronize(s->stream));
     queued = wide ? s->h_msum[4] : 0;
     if (queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
     if (!wide || queued <= w.qcap) break;
   }
   *nr = s->h_msum[0];
-  const uint64_t items = s->h_msum[3];
-  if (*nr > n || items > 64 * (n - *nr) + ((uint64_t)kReScanLimit + 1) * queued)
+  const uint64_t hex_items = s->h_msum[3];
+  if (*nr > n || hex_items > 64 * (n - *nr) + ((uint64_t)kReScanLimit + 1) * queued)
     return YR_AMD_INTERNAL_FATAL_ERROR;
+  // the confirmed heads: at most one per record that left the rest
+  const uint64_t chain_items = chains ? (uint32_t)s->h_msum[5] : 0;
+  if (chain_items > n - *nr) return YR_AMD_INTERNAL_FATAL_ERROR;
+  const uint64_t items = hex_items + chain_items;
   if (debug_level() >= 1 && wide)
     fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_device()\n",
             (unsigned long long)n, (unsigned long long)queued);
@@ -1884,6 +1956,14 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
     HIP_TRY(launch_hex_wide_expand(w, wide_waves, s->stream));
   } else {
     HIP_TRY(launch_hex_expand(p, s->stream));
+  }
+  if (chain_items > 0) {
+    // behind the records' items, in confirm order: the sort is stable, so of
+    // two confirmations of one (head, offset) the first stays first
+    HIP_TRY(hipMemcpyAsync(p.ikeys + hex_items, c.item_keys, chain_items * sizeof(uint64_t),
+                           hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(p.iindex + hex_items, c.item_index, chain_items * sizeof(uint32_t),
+                           hipMemcpyDeviceToDevice, s->stream));
   }
   int sorted = 0;
   HIP_TRY(match_sort(keys, index, items, lo_bits, hi_bits, s->d_mhist, s->d_mhchunk, s->d_mhsum + 2,
@@ -1928,6 +2008,110 @@ int yr_amd_tables_match_strings(const yr_amd_tables* t, uint32_t classes, uint8_
   return YR_AMD_SUCCESS;
 }
 
+// ---- Chained strings (matches.h ChainTables; chains.hip) ----
+
+int yr_amd_tables_set_chains(yr_amd_tables* t, const uint32_t* chained_to, const int32_t* gap_min,
+                             const int32_t* gap_max, uint32_t n_strings) {
+  if (t == nullptr || t->has_chains || !(t->has_strings || t->has_str_flags) ||
+      n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && (chained_to == nullptr || gap_min == nullptr || gap_max == nullptr)))
+    return YR_AMD_INVALID_ARGUMENT;
+  const std::vector<uint32_t>& flags = t->h_str_flags;
+  // a chain is a path: every string links to at most one, is linked by at most one
+  std::vector<uint32_t> next(n_strings, kNoChain);   // the string chained to k
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    if (gap_min[k] < 0 || gap_max[k] < gap_min[k]) return YR_AMD_INVALID_ARGUMENT;
+    const uint32_t to = chained_to[k];
+    if (to == kNoChain) continue;
+    if (to >= n_strings || to == k || !(flags[k] & kStrChainPart) || !(flags[to] & kStrChainPart) ||
+        next[to] != kNoChain)
+      return YR_AMD_INVALID_ARGUMENT;
+    next[to] = k;
+  }
+  std::vector<uint32_t> chain_of(n_strings, kNoChain), level_of(n_strings, 0), off{0}, strs;
+  std::vector<uint8_t> settled;
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    const bool linked = chained_to[k] != kNoChain, target = next[k] != kNoChain;
+    // the tail, and only the tail, carries CHAIN_TAIL
+    if (((flags[k] & kStrChainTail) != 0) != (linked && !target)) return YR_AMD_INVALID_ARGUMENT;
+    if (linked || !target) continue;
+    // a head: down the chain to its tail
+    const uint32_t chain = (uint32_t)settled.size();
+    uint8_t ok = 3;
+    for (uint32_t j = k; j != kNoChain; j = next[j]) {
+      chain_of[j] = chain;
+      level_of[j] = (uint32_t)strs.size() - off.back();
+      strs.push_back(j);
+      for (uint32_t cls : {kMatchLiteral, kMatchLiteral | kMatchHex})
+        if (!string_settles_in_chain(flags[j], cls)) ok &= (uint8_t)~(1u << (cls >> 1));
+    }
+    // (a level's state is a lane's: a longer chain stays with the host)
+    if (strs.size() - off.back() > kChainMaxLevels) ok = 0;
+    off.push_back((uint32_t)strs.size());
+    settled.push_back(ok);
+  }
+  // a linked string no head leads to lies on a cycle
+  for (uint32_t k = 0; k < n_strings; ++k)
+    if (chained_to[k] != kNoChain && chain_of[k] == kNoChain) return YR_AMD_INVALID_ARGUMENT;
+  const uint32_t n_chains = (uint32_t)settled.size();
+  if (t->device >= 0) {
+    // one allocation: chain_of, level_of, gap_min, gap_max, chain_off, chain_strs, settled
+    HIP_TRY(hipSetDevice(t->device));
+    std::vector<uint32_t> w;
+    w.insert(w.end(), chain_of.begin(), chain_of.end());
+    w.insert(w.end(), level_of.begin(), level_of.end());
+    for (uint32_t k = 0; k < n_strings; ++k) w.push_back((uint32_t)gap_min[k]);
+    for (uint32_t k = 0; k < n_strings; ++k) w.push_back((uint32_t)gap_max[k]);
+    w.insert(w.end(), off.begin(), off.end());
+    w.insert(w.end(), strs.begin(), strs.end());
+    const size_t at_settled = w.size();
+    w.resize(at_settled + (n_chains + 3) / 4, 0);
+    if (n_chains > 0) memcpy(w.data() + at_settled, settled.data(), n_chains);
+    int r = upload(t->d_chain_words, w.data(), w.size());
+    if (r) {
+      if (t->d_chain_words) (void)hipFree(t->d_chain_words);
+      t->d_chain_words = nullptr;
+      return r;
+    }
+    const uint32_t* d = t->d_chain_words;
+    ChainTables& c = t->d_chain;
+    c.chain_of = d;
+    c.level_of = d + n_strings;
+    c.gap_min = reinterpret_cast<const int32_t*>(d + 2 * (size_t)n_strings);
+    c.gap_max = reinterpret_cast<const int32_t*>(d + 3 * (size_t)n_strings);
+    c.chain_off = d + 4 * (size_t)n_strings;
+    c.chain_strs = c.chain_off + off.size();
+    c.settled = reinterpret_cast<const uint8_t*>(d + at_settled);
+    c.n_chains = n_chains;
+  }
+  t->h_chain_of = std::move(chain_of);
+  t->h_chain_off = std::move(off);
+  t->h_chain_strs = std::move(strs);
+  t->h_chain_settled = std::move(settled);
+  t->has_chains = true;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_tables_chain_strings(const yr_amd_tables* t, uint32_t classes, uint8_t* out,
+                                uint32_t n_strings) {
+  if (t == nullptr || !(t->has_strings || t->has_str_flags) || n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && out == nullptr) || !t->has_chains)
+    return YR_AMD_INVALID_ARGUMENT;
+  if (!(classes & YR_AMD_MATCH_LITERAL) || (classes & ~(YR_AMD_MATCH_LITERAL | YR_AMD_MATCH_HEX)))
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    const uint32_t c = t->h_chain_of[k];
+    out[k] = c != kNoChain && ((t->h_chain_settled[c] >> (classes >> 1)) & 1u) ? 1 : 0;
+  }
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scanner_set_chains(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->chains = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_match_rec** d_matches,
                         uint64_t* n_matches, const yr_amd_verify_rec** d_rest, uint64_t* n_rest) {
   if (s == nullptr || s->pending || !s->scanned || s->batch || !s->tables->has_strings)
@@ -1942,14 +2126,20 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
   // the hex class interprets the strings' programs (yr_amd_tables_set_re_code)
   const bool hex = (s->match_classes & kMatchHex) != 0;
   if (hex && t->d_re_code == nullptr) return YR_AMD_INVALID_ARGUMENT;
+  // chained strings (yr_amd_scanner_set_chains): of a whole-block scan only -- a
+  // shard does not see the other parts, its chain records stay in the rest
+  if (s->chains && !t->has_chains) return YR_AMD_INVALID_ARGUMENT;
+  const bool chains = s->chains && t->d_chain.n_chains > 0 && s->win_lo == 0 &&
+                      s->win_hi == s->last.block_size && s->last.byte_begin == 0 &&
+                      s->last.byte_end == s->last.block_size;
   const yr_amd_verify_rec* d_rec = nullptr;
   uint64_t n = 0;
   int r = yr_amd_verify_device(s, data_base, &d_rec, &n);
   if (r) return r;
   if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   uint64_t nm = 0, nr = 0;
-  if (n > 0 && hex) {
-    r = match_device_hex(s, d_rec, n, &nm, &nr);
+  if (n > 0 && (hex || chains)) {   // (the events are assembled behind the records' measure pass)
+    r = match_device_hex(s, d_rec, n, &nm, &nr, chains);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n);
@@ -2005,7 +2195,8 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
             (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
   if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
   if (n_matches) *n_matches = nm;
-  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex ? s->d_hrest : s->d_mrest);
+  if (d_rest)
+    *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex || chains ? s->d_hrest : s->d_mrest);
   if (n_rest) *n_rest = nr;
   return YR_AMD_SUCCESS;
 }
@@ -2019,6 +2210,7 @@ int yr_amd_scan_block_matches(yr_amd_scanner* s, const uint8_t* data, size_t siz
   if ((uint64_t)size > YR_AMD_MATCH_MAX_BLOCK) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
   if ((s->match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
     return YR_AMD_INVALID_ARGUMENT;
+  if (s->chains && !s->tables->has_chains) return YR_AMD_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(s->tables->device));
   int rg = grow(s->d_block, s->d_block_cap, std::max<size_t>(size, 16));
   if (rg) return rg;

@@ -218,6 +218,22 @@ extern "C" int yr_amd_tables_load_yarc(const uint8_t* file, size_t file_size, in
     }
   }
 
+  // the chain links (yr_amd_tables_set_chains)
+  std::vector<uint32_t> chained(n_strings ? n_strings : 1, 0xFFFFFFFFu);
+  std::vector<int32_t> gmin(n_strings ? n_strings : 1, 0), gmax(n_strings ? n_strings : 1, 0);
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    const uint8_t* s = a.data[kStringsTable] + (uint64_t)k * kStringSize;
+    Ref rc;
+    if (!a.ref(kStringsTable, (uint64_t)k * kStringSize + 32, rc)) return YR_AMD_INVALID_ARGUMENT;
+    if (!rc.null()) {
+      if (rc.buffer != kStringsTable || rc.offset % kStringSize || rc.offset / kStringSize >= n_strings)
+        return YR_AMD_INVALID_ARGUMENT;
+      chained[k] = rc.offset / kStringSize;
+      gmin[k] = rd<int32_t>(s + 40);   // (meaningful on a linked string only)
+      gmax[k] = rd<int32_t>(s + 44);
+    }
+  }
+
   yr_amd_tables* t = nullptr;
   r = yr_amd_tables_create(T.data(), M.data(), n_slots, nx.data(), bt.data(), n_pool, device, &t);
   if (r) return r;
@@ -243,6 +259,11 @@ extern "C" int yr_amd_tables_load_yarc(const uint8_t* file, size_t file_size, in
       yr_amd_tables_destroy(t);
       return r;
     }
+  }
+  r = yr_amd_tables_set_chains(t, chained.data(), gmin.data(), gmax.data(), n_strings);
+  if (r) {
+    yr_amd_tables_destroy(t);
+    return r;
   }
   *tables = t;
   return YR_AMD_SUCCESS;
