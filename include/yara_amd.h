@@ -654,7 +654,8 @@ int yr_amd_tables_match_strings(
  * tables without chain records.
  *
  * yr_amd_scanner_set_chains(1): yr_amd_match_device and
- * yr_amd_scan_block_matches (the batch calls never read it) also report the
+ * yr_amd_scan_block_matches (the batch calls never read it: theirs is
+ * yr_amd_scanner_set_batch_chains below) also report the
  * settled chains' matches, exactly libyara's lists:
  *   - the events of a chain are its parts' kept records in record order, each
  *     measured as a final string of its class is (a hex part by the
@@ -971,6 +972,51 @@ int yr_amd_scanner_set_batch_match_classes(yr_amd_scanner* scanner, uint32_t cla
  * the first wait sees it, the queue grows and the measure pass runs again.
  */
 int yr_amd_scanner_set_batch_hex_wide(yr_amd_scanner* scanner, int enable);
+
+/*
+ * The batch's chained strings.  0 (default): every record of a chain part of a
+ * batch stays in the rest, and the batch stage launches exactly what it
+ * launches without this setting.  1: yr_amd_match_batch_device and
+ * yr_amd_scan_batch_matches (and through them gathered batches) also report
+ * the settled chains' matches, per buffer, as yr_amd_scanner_set_chains does
+ * for a single block.  Read only by the batch match calls; the single-block
+ * calls never read it, and the batch calls still never read
+ * yr_amd_scanner_set_chains.  Settled chains are those of
+ * yr_amd_tables_chain_strings with the BATCH classes.
+ *
+ * With the setting on, buffer k of a batch gets exactly the matches and the
+ * rest that yr_amd_scan_block_matches(data_k, size_k, bases[k]) returns for
+ * that buffer alone on a scanner with yr_amd_scanner_set_chains(1) and the
+ * same classes and wide setting:
+ *   - the events of a (buffer, chain) pair are that buffer's kept records of
+ *     the chain's parts in record order, each measured inside its own buffer
+ *     (local offsets; the buffer is the whole block of both hex runs);
+ *   - dirtiness is per (buffer, chain): a record that is not exactly one event
+ *     (more than one backward result, a set past the 64 positions -- with the
+ *     batch's wave-wide path on as well --, no forward program) leaves all of
+ *     THAT BUFFER's records of the chain in the rest, in place, yields nothing
+ *     there and touches no other buffer;
+ *   - a chain never spans buffers: a head at the end of buffer k and a tail at
+ *     the start of buffer k + 1 confirm nothing;
+ *   - confirmed heads are matches {head string, local offset, tail offset -
+ *     offset + tail length, xor_key 0, pool_index of the head's record} in the
+ *     buffer's one ascending (string, offset) list, the first confirmation of
+ *     an offset kept; match_off[] and rest_off[] count them.
+ * The device workspace grows with the batch's record count and its buffer
+ * count, never with buffers x chains or buffers x strings.  With the setting
+ * on and no chain records on the tables the batch match calls return
+ * YR_AMD_INVALID_ARGUMENT.  The stage still waits twice (with the literal
+ * class alone and chains on: twice instead of once): everything added is
+ * queued ahead of the first wait.  NULL scanner or a value other than 0/1:
+ * YR_AMD_INVALID_ARGUMENT.
+ *
+ * yr_amd_scanner_batch_chain_waves: the number of waves of the replay's grid,
+ * one (buffer, chain) group per wave at a time; a batch with more groups is
+ * worked off by the same waves in turn.  NULL scanner or NULL waves:
+ * YR_AMD_INVALID_ARGUMENT.
+ */
+int yr_amd_scanner_set_batch_chains(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
+int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* scanner, uint32_t* waves);
 
 /*
  * ---- Block pipeline ----

@@ -47,8 +47,11 @@ reference takes from its list's order.
 that libyara split at a jump wider than 200 bytes is printed as matches of its
 first part, the chain's head, assembled on the GPU as stock libyara assembles
 them.  The parts are settled as the classes settle strings: literal parts
-always, parts with wildcards with --hex.  Chains are per block, and the batch
-calls do not settle them: with --chains every file takes the block path.
+always, parts with wildcards with --hex.  A chain lies within one block; a file
+above BLOCK bytes gets the chains each of its blocks holds whole.  Several files
+go through batches as without --chains (yr_amd_scanner_set_batch_chains), each
+file's chains assembled inside the file: only the files above BLOCK bytes take
+the block path.
 """
 import gzip
 import os
@@ -116,6 +119,7 @@ def main():
     sc.set_hex_wide(hex_wide)
     sc.set_batch_hex_wide(hex_wide)
     sc.set_chains(chains)
+    sc.set_batch_chains(chains)
     paths = argv[1:]
     if len(paths) == 1:
         matches, left = block_path(sc, np.fromfile(paths[0], dtype=np.uint8))
@@ -125,7 +129,7 @@ def main():
         return
     sizes = [os.path.getsize(p) for p in paths]
     per, left = [None] * len(paths), 0
-    for group in ([] if chains else arenas(sizes)):
+    for group in arenas(sizes):
         try:
             m, mo, rest, _ = sc.batch_string_matches(
                 [np.fromfile(paths[k], dtype=np.uint8) for k in group])
@@ -137,7 +141,7 @@ def main():
             per[k] = m[int(mo[j]):int(mo[j + 1])]
         left += len(rest)
     for k, p in enumerate(paths):
-        if per[k] is None:   # larger than BLOCK, or --chains
+        if per[k] is None:   # larger than BLOCK
             per[k], n = block_path(sc, np.fromfile(p, dtype=np.uint8))
             left += n
         for r in per[k]:

@@ -296,6 +296,7 @@ class Scanner:
         self._batch_classes = MATCH_LITERAL   # set_batch_match_classes
         self._hex_wide = False   # set_hex_wide
         self._batch_hex_wide = False   # set_batch_hex_wide
+        self._batch_chains = False   # set_batch_chains
         self._chains = False   # set_chains
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
@@ -384,7 +385,7 @@ class Scanner:
         """Settle chained hex strings too (yr_amd_scanner_set_chains): the
         matches of the heads of the chains ``Tables.chain_strings`` names, as
         stock libyara assembles them.  The tables need chain records; the
-        batch calls never read it."""
+        batch calls never read it (theirs is set_batch_chains)."""
         _lib.check("yr_amd_scanner_set_chains",
                    _lib.lib().yr_amd_scanner_set_chains(self._h, int(enable)))
         self._chains = bool(enable)
@@ -434,20 +435,45 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_batch_hex_wide(self._h, int(enable)))
         self._batch_hex_wide = bool(enable)
 
-    def _with_batch_hex(self, hex, call, wide=False):
+    def set_batch_chains(self, enable: bool):
+        """Settle chained hex strings in the BATCH match stage too
+        (yr_amd_scanner_set_batch_chains): per buffer, what ``set_chains`` gives
+        for that buffer alone, the settled chains those of
+        ``Tables.chain_strings`` with the batch classes.  Read only by the
+        batch calls; the tables need chain records."""
+        _lib.check("yr_amd_scanner_set_batch_chains",
+                   _lib.lib().yr_amd_scanner_set_batch_chains(self._h, int(enable)))
+        self._batch_chains = bool(enable)
+
+    def batch_chain_waves(self) -> int:
+        """The waves of the batch chain replay's grid
+        (yr_amd_scanner_batch_chain_waves): a batch with more (buffer, chain)
+        groups is worked off by the same waves in turn."""
+        w = ctypes.c_uint32()
+        _lib.check("yr_amd_scanner_batch_chain_waves",
+                   _lib.lib().yr_amd_scanner_batch_chain_waves(self._h, ctypes.byref(w)))
+        return w.value
+
+    def _with_batch_hex(self, hex, call, wide=False, chains=False):
         # _with_hex for the batch calls' settings
         was, was_wide = self._batch_classes, self._batch_hex_wide
         if not hex or (was & MATCH_HEX):
             hex = False
         if not wide or was_wide:
             wide = False
+        if not chains or self._batch_chains:
+            chains = False
         if hex:
             self.set_batch_match_classes(was | MATCH_HEX)
         if wide:
             self.set_batch_hex_wide(True)
+        if chains:
+            self.set_batch_chains(True)
         try:
             return call()
         finally:
+            if chains:
+                self.set_batch_chains(False)
             if wide:
                 self.set_batch_hex_wide(False)
             if hex:
@@ -646,7 +672,8 @@ class Scanner:
         return self.verify_batch_device(bases)
 
     # -- final matches of a batch ------------------------------------------------
-    def match_batch_device(self, bases=None, hex: bool = False, wide: bool = False):
+    def match_batch_device(self, bases=None, hex: bool = False, wide: bool = False,
+                           chains: bool = False):
         """(matches, match_off, rest, rest_off) of the last completed batch scan
         (yr_amd_match_batch_device), copied to the host: buffer k's
         ``matches[match_off[k]:match_off[k + 1]]`` and
@@ -657,8 +684,10 @@ class Scanner:
         leaves the scanner's batch classes (set_batch_match_classes) as they
         are.  ``wide=True`` turns the batch's wave-wide path on for this call
         (set_batch_hex_wide), as ``string_matches(hex=True, wide=True)`` does
-        for the buffer alone: by itself it does nothing."""
-        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide)
+        for the buffer alone: by itself it does nothing.  ``chains=True``
+        settles the chained strings for this call (set_batch_chains), as
+        ``string_matches(chains=True)`` does for the buffer alone."""
+        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide, chains)
 
     def _match_batch_device(self, bases):
         from ._hip import memcpy
@@ -680,12 +709,15 @@ class Scanner:
             memcpy(rest.ctypes.data, pr.value, rest.size * 16, 2)
         return matches, match_off, rest, rest_off
 
-    def batch_string_matches(self, buffers, bases=None, hex: bool = False, wide: bool = False):
+    def batch_string_matches(self, buffers, bases=None, hex: bool = False, wide: bool = False,
+                             chains: bool = False):
         """(matches, match_off, rest, rest_off) of a list of host buffers
         (yr_amd_scan_batch_matches): buffer k's slices equal
-        ``string_matches(buffers[k], bases[k], hex=hex, wide=wide)``.  One scan,
-        one pre-verification and one match stage for all of them."""
-        return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases), wide)
+        ``string_matches(buffers[k], bases[k], hex=hex, wide=wide,
+        chains=chains)``.  One scan, one pre-verification and one match stage
+        for all of them."""
+        return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases), wide,
+                                    chains)
 
     def _batch_string_matches(self, buffers, bases):
         bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
@@ -713,7 +745,7 @@ class Scanner:
         return matches, match_off, rest, rest_off
 
     def batch_string_matches_device(self, buffers, bases=None, hex: bool = False,
-                                    wide: bool = False):
+                                    wide: bool = False, chains: bool = False):
         """batch_string_matches for buffers in device memory (see
         batch_candidates_device), through the gather call."""
         ptrs, sizes = _device_buffers(buffers)
@@ -721,7 +753,7 @@ class Scanner:
             raise ValueError("one base per buffer")
         self.scan_batch_gather_device(ptrs, sizes)
         self.batch_result()
-        return self.match_batch_device(bases, hex=hex, wide=wide)
+        return self.match_batch_device(bases, hex=hex, wide=wide, chains=chains)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

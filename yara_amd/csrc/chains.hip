@@ -30,6 +30,10 @@
 //
 // A wave touches no other chain's state; the only atomics are the dirty flags,
 // the per-string counts and the item counter.
+//
+// The batch (yr_amd_scanner_set_batch_chains; BatchChainParams, DESIGN.md
+// 18.7) replays the same procedure -- the same device functions -- one wave per
+// (buffer, chain) group found in the sorted stream of events.
 #include "internal.h"
 #include "matches.h"
 #include "match_measure.h"
@@ -273,10 +277,125 @@ __device__ uint32_t chain_mark(const Lists& L, uint32_t base, uint32_t n, int64_
   return count;
 }
 
+// Where the confirmed heads go: items {head << 32 | offset, the head's record},
+// one atomic per step of the sweep.
+struct ChainSink {
+  uint64_t* item_keys;
+  uint32_t* item_index;
+  uint32_t* item_count;
+};
+
+// scan.c:546-583 on the head's list [base, base + n) at a tail match {moff,
+// mlen}: the entries with the full chain length leave as items, the others
+// close up.  Returns the new length; `confirmed` counts the items.
+__device__ __forceinline__ uint32_t chain_confirm(const Lists& L, uint32_t base, uint32_t n,
+                                                  uint32_t levels, uint32_t head, uint32_t moff,
+                                                  uint32_t mlen, const MatchParams& p,
+                                                  const ChainSink& k, uint32_t& confirmed) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t w = 0;
+  for (uint32_t b = 0; b < n; b += 64) {
+    const uint32_t i = b + lane;
+    const bool v = i < n;
+    uint32_t o = 0, l = 0, cl = 0, rc = 0;
+    if (v) {
+      o = L.off[base + i];
+      l = L.len[base + i];
+      cl = L.cl[base + i] & ~kChainNew;
+      rc = L.rec[base + i];
+    }
+    const bool done = v && cl == levels - 1;
+    const uint64_t D = __ballot(done), K = __ballot(v && !done);
+    if (D != 0) {
+      uint32_t slot = 0;
+      if (lane == 0) slot = atomicAdd(k.item_count, (uint32_t)__popcll(D));
+      slot = lane_of(slot, 0) + lanes_below(D);
+      if (done && slot < p.n) {
+        k.item_keys[slot] = (uint64_t)head << 32 | o;
+        k.item_index[slot] = rc;
+        // hex_unique_kernel adds the record's distance from the item's offset
+        MatchMeasure m;
+        m.length = moff + mlen - (uint32_t)p.recs[rc].offset;
+        m.xor_key = 0;
+        p.meas[rc] = m;
+      }
+      confirmed += (uint32_t)__popcll(D);
+    }
+    const uint32_t at = w + lanes_below(K);
+    if (v && !done && at != i) {
+      L.off[base + at] = o;
+      L.len[base + at] = l;
+      L.cl[base + at] = cl;
+      L.rec[base + at] = rc;
+    }
+    w += (uint32_t)__popcll(K);
+  }
+  return w;
+}
+
+// One event {lvl, moff, mlen, mrec} of a chain of `levels` parts, the whole of
+// _yr_scan_verify_chained_string_match for that call.  Level l's state is lane
+// l's: its list's place lbase and length llen, its gaps lgmin / lgmax.
+__device__ __forceinline__ void chain_event(const Lists& L, uint32_t levels, uint32_t head,
+                                            uint32_t lvl, uint32_t moff, uint32_t mlen,
+                                            uint32_t mrec, uint32_t lbase, uint32_t& llen,
+                                            int32_t lgmin, int32_t lgmax, const MatchParams& p,
+                                            const ChainSink& k, uint32_t& confirmed) {
+  const uint32_t lane = threadIdx.x & 63u;
+  if (lvl >= levels) return;   // (never: level_of is below the chain's length)
+  const bool tail = lvl + 1 == levels;
+  if (lvl != 0) {
+    // scan.c:452-498 on the list of the part before this one
+    const uint32_t own = tail ? 0u : lane_of(llen, lvl);
+    const int64_t lowest = own != 0 ? (int64_t)uni(L.off[lane_of(lbase, lvl)]) : (int64_t)moff;
+    const int64_t gmin = (int32_t)lane_of((uint32_t)lgmin, lvl);
+    const int64_t gmax = (int32_t)lane_of((uint32_t)lgmax, lvl);
+    bool found;
+    const uint32_t left = chain_prune(L, lane_of(lbase, lvl - 1), lane_of(llen, lvl - 1), moff,
+                                      lowest, gmin, gmax, found);
+    if (lane == lvl - 1) llen = left;
+    if (!found) return;
+    if (tail) {
+      // scan.c:519-534, the recursion a frontier per level: level lv's new
+      // entries mark level lv - 1 with the next chain length
+      uint32_t fresh = chain_mark(L, lane_of(lbase, lvl - 1), left, moff, gmin, gmax, 1u);
+      for (uint32_t lv = lvl - 1; lv != 0 && fresh != 0; --lv) {
+        const uint32_t base = lane_of(lbase, lv), n = lane_of(llen, lv);
+        const int64_t g0 = (int32_t)lane_of((uint32_t)lgmin, lv);
+        const int64_t g1 = (int32_t)lane_of((uint32_t)lgmax, lv);
+        const uint32_t val = levels - lv;
+        fresh = 0;
+        for (uint32_t b = 0; b < n; b += 64) {
+          const uint32_t i = b + lane;
+          uint32_t cl = 0, o = 0;
+          if (i < n) {
+            cl = L.cl[base + i];
+            o = L.off[base + i];
+            if (cl & kChainNew) L.cl[base + i] = cl & ~kChainNew;
+          }
+          for (uint64_t N = __ballot((cl & kChainNew) != 0); N != 0; N &= N - 1)
+            fresh += chain_mark(L, lane_of(lbase, lv - 1), lane_of(llen, lv - 1),
+                                (int64_t)lane_of(o, (uint32_t)__builtin_ctzll(N)), g0, g1, val);
+        }
+      }
+      // scan.c:546-583: the head's entries with the full chain length are matches
+      const uint32_t w = chain_confirm(L, lane_of(lbase, 0), lane_of(llen, 0), levels, head, moff,
+                                       mlen, p, k, confirmed);
+      if (lane == 0) llen = w;
+      lists_fence();
+      return;
+    }
+  }
+  // scan.c:585-628: a part that is not the tail joins its unconfirmed list
+  const uint32_t n = chain_insert(L, lane_of(lbase, lvl), lane_of(llen, lvl), moff, mlen, mrec);
+  if (lane == lvl) llen = n;
+}
+
 __global__ __launch_bounds__(64 * kChainWaves) void chain_replay_kernel(ChainParams c, uint32_t waves) {
   __shared__ uint32_t share[kChainWaves][4 * kChainLdsEntries];
   const MatchParams& p = c.h.m;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const ChainSink sink{c.item_keys, c.item_index, c.item_count};
   for (uint32_t chain = blockIdx.x * kChainWaves + wave; chain < c.t.n_chains; chain += waves) {
     const uint32_t begin = uni(c.cbegin[chain]), end = uni(c.cend[chain]);
     if (begin >= end) continue;
@@ -305,6 +424,7 @@ __global__ __launch_bounds__(64 * kChainWaves) void chain_replay_kernel(ChainPar
     L.cl = L.len + stride;
     L.rec = L.cl + stride;
     const uint32_t head = lane_of(lstr, 0);
+    uint32_t confirmed = 0;
 
     for (uint32_t eb = begin; eb < end; eb += 64) {
       const uint32_t cnt = min(64u, end - eb);
@@ -315,94 +435,208 @@ __global__ __launch_bounds__(64 * kChainWaves) void chain_replay_kernel(ChainPar
         eoff = c.ev_offset[erec];
         elen = c.ev_length[erec];
       }
-      for (uint32_t j = 0; j < cnt; ++j) {
-        const uint32_t lvl = lane_of(elvl, j), moff = lane_of(eoff, j), mlen = lane_of(elen, j);
-        const uint32_t mrec = lane_of(erec, j);
-        if (lvl >= levels) continue;   // (never: level_of is below the chain's length)
-        const bool tail = lvl + 1 == levels;
-        if (lvl != 0) {
-          // scan.c:452-498 on the list of the part before this one
-          const uint32_t own = tail ? 0u : lane_of(llen, lvl);
-          const int64_t lowest = own != 0 ? (int64_t)uni(L.off[lane_of(lbase, lvl)]) : (int64_t)moff;
-          const int64_t gmin = (int32_t)lane_of((uint32_t)lgmin, lvl);
-          const int64_t gmax = (int32_t)lane_of((uint32_t)lgmax, lvl);
-          bool found;
-          const uint32_t left = chain_prune(L, lane_of(lbase, lvl - 1), lane_of(llen, lvl - 1), moff,
-                                            lowest, gmin, gmax, found);
-          if (lane == lvl - 1) llen = left;
-          if (!found) continue;
-          if (tail) {
-            // scan.c:519-534, the recursion a frontier per level: level lv's new
-            // entries mark level lv - 1 with the next chain length
-            uint32_t fresh = chain_mark(L, lane_of(lbase, lvl - 1), left, moff, gmin, gmax, 1u);
-            for (uint32_t lv = lvl - 1; lv != 0 && fresh != 0; --lv) {
-              const uint32_t base = lane_of(lbase, lv), n = lane_of(llen, lv);
-              const int64_t g0 = (int32_t)lane_of((uint32_t)lgmin, lv);
-              const int64_t g1 = (int32_t)lane_of((uint32_t)lgmax, lv);
-              const uint32_t val = levels - lv;
-              fresh = 0;
-              for (uint32_t b = 0; b < n; b += 64) {
-                const uint32_t i = b + lane;
-                uint32_t cl = 0, o = 0;
-                if (i < n) {
-                  cl = L.cl[base + i];
-                  o = L.off[base + i];
-                  if (cl & kChainNew) L.cl[base + i] = cl & ~kChainNew;
-                }
-                for (uint64_t N = __ballot((cl & kChainNew) != 0); N != 0; N &= N - 1)
-                  fresh += chain_mark(L, lane_of(lbase, lv - 1), lane_of(llen, lv - 1),
-                                      (int64_t)lane_of(o, (uint32_t)__builtin_ctzll(N)), g0, g1, val);
-              }
-            }
-            // scan.c:546-583: the head's entries with the full chain length are matches
-            const uint32_t base = lane_of(lbase, 0), n = lane_of(llen, 0);
-            uint32_t w = 0;
-            for (uint32_t b = 0; b < n; b += 64) {
-              const uint32_t i = b + lane;
-              const bool v = i < n;
-              uint32_t o = 0, l = 0, cl = 0, rc = 0;
-              if (v) {
-                o = L.off[base + i];
-                l = L.len[base + i];
-                cl = L.cl[base + i] & ~kChainNew;
-                rc = L.rec[base + i];
-              }
-              const bool done = v && cl == levels - 1;
-              const uint64_t D = __ballot(done), K = __ballot(v && !done);
-              if (D != 0) {
-                uint32_t slot = 0;
-                if (lane == 0) slot = atomicAdd(c.item_count, (uint32_t)__popcll(D));
-                slot = lane_of(slot, 0) + lanes_below(D);
-                if (done && slot < p.n) {
-                  c.item_keys[slot] = (uint64_t)head << 32 | o;
-                  c.item_index[slot] = rc;
-                  // hex_unique_kernel adds the record's distance from the item's offset
-                  MatchMeasure m;
-                  m.length = moff + mlen - (uint32_t)p.recs[rc].offset;
-                  m.xor_key = 0;
-                  p.meas[rc] = m;
-                }
-              }
-              const uint32_t at = w + lanes_below(K);
-              if (v && !done && at != i) {
-                L.off[base + at] = o;
-                L.len[base + at] = l;
-                L.cl[base + at] = cl;
-                L.rec[base + at] = rc;
-              }
-              w += (uint32_t)__popcll(K);
-            }
-            if (lane == 0) llen = w;
-            lists_fence();
-            continue;
-          }
-        }
-        // scan.c:585-628: a part that is not the tail joins its unconfirmed list
-        const uint32_t n = chain_insert(L, lane_of(lbase, lvl), lane_of(llen, lvl), moff, mlen, mrec);
-        if (lane == lvl) llen = n;
-      }
+      for (uint32_t j = 0; j < cnt; ++j)
+        chain_event(L, levels, head, lane_of(elvl, j), lane_of(eoff, j), lane_of(elen, j),
+                    lane_of(erec, j), lbase, llen, lgmin, lgmax, p, sink, confirmed);
     }
   }
+}
+
+// ---- The batch's chains (matches.h BatchChainParams) ----
+// The same replay, one wave per (buffer, chain) GROUP.  Nothing is indexed by
+// (buffer, chain) or (buffer, string): the groups are found in the events'
+// stream once batch_match_sort has ordered it by (buffer, chain), and each
+// group's lists live in the group's own slots of that stream.
+
+__global__ __launch_bounds__(256) void batch_chain_clear_kernel(BatchChainParams c) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= c.b.nbuf) c.buf_items[i] = 0;
+  if (i < 2) c.counts[i] = 0;
+}
+
+// chain_events_kernel with batch_hex_measure_kernel's view: the record's buffer
+// (buf[], the measure pass has searched for it) is the whole block of both
+// runs, offsets are local to it.  An event and a dirty-maker both get their
+// chain as the sort's key -- dirtiness is a property of the (buffer, chain)
+// group, derived from the group's run, so no flag array is written here.
+__global__ __launch_bounds__(256) void batch_chain_events_kernel(BatchChainParams c) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const MatchParams& p = c.b.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= p.n) return;
+  const VerifyRec rec = p.recs[r];
+  const uint32_t string = p.pool_string[rec.pool_index];
+  const uint32_t chain = string < p.n_strings ? c.t.chain_of[string] : kNoChain;
+  const uint32_t k = c.b.buf[r];
+  uint32_t key = c.t.n_chains;
+  if (chain != kNoChain && k < c.b.nbuf && ((c.t.settled[chain] >> (c.b.h.classes >> 1)) & 1u)) {
+    HexMatchParams q = c.b.h;
+    q.m.data = p.data + c.b.starts[k];
+    q.m.size = c.b.sizes[k];
+    q.m.win_lo = 0;
+    q.m.win_hi = q.m.size;
+    DevPoolRec e = p.pool[rec.pool_index];
+    e.flags &= ~(kStrChainPart | kStrChainTail);
+    MatchMeasure m{0, 0};
+    uint64_t offset = rec.offset;
+    bool event = false, dirty = false;
+    if (string_is_final(e.flags)) {
+      event = measure(q.m, e, rec.offset, m);
+    } else {
+      HexSet set{1ull, 0u, 0u};
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      const int v = measure_hex(q, e, rec.offset, buf, m, set);
+      if (v == kHexMatch && m.length != 0) {
+        // one callback per backward result, in an order that is not restated
+        dirty = (set.mask & (set.mask - 1)) != 0;
+        const uint32_t B = set.base + (uint32_t)__builtin_ctzll(set.mask);
+        offset -= B;   // (B <= min(offset, YR_RE_SCAN_LIMIT))
+        m.length += B;
+        event = !dirty;
+      } else {
+        dirty = v == kHexUndecided;
+      }
+    }
+    if (event || dirty) {
+      key = chain;
+      c.ev_level[r] = dirty ? kChainDirtyMaker : c.t.level_of[string];
+      c.ev_offset[r] = (uint32_t)offset;   // (below the buffer's size)
+      c.ev_length[r] = m.length;
+    }
+  }
+  c.skeys[r] = key;
+  c.sindex[r] = (uint32_t)r;
+}
+
+// One lane per sorted entry: the first entry of a (buffer, chain) run appends
+// the run's place to the group list -- one atomic per wave, the list in no
+// particular order.
+__global__ __launch_bounds__(256) void batch_chain_groups_kernel(BatchChainParams c) {
+  const uint64_t n = c.b.h.m.n;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool first = false;
+  if (i < n) {
+    const uint64_t key = c.sorted_keys[i];
+    first = key < c.t.n_chains &&
+            (i == 0 || c.sorted_keys[i - 1] != key ||
+             c.b.buf[c.sorted_index[i - 1]] != c.b.buf[c.sorted_index[i]]);
+  }
+  const uint64_t F = __ballot(first);
+  if (F == 0) return;   // (wave-uniform)
+  uint32_t slot = 0;
+  if ((threadIdx.x & 63u) == 0) slot = atomicAdd(c.counts, (uint32_t)__popcll(F));
+  slot = lane_of(slot, 0) + lanes_below(F);
+  if (first && slot < n) c.gbegin[slot] = (uint32_t)i;
+}
+
+// One WAVE per group, a fixed grid striding over the group list (its length is
+// read here, not waited for).  The wave walks its run twice.  First to its end
+// -- the run is contiguous: the entries that share the first one's chain and
+// buffer -- looking for a dirty-maker and counting the events per level into
+// lane `level`: a level's list holds at most its own events, so the prefix sum
+// of the counts places every list inside the run's own E slots, of the wave's
+// LDS share (E <= kChainLdsEntries) or of the [4][n] workspace at `begin`.  A
+// dirty group is left as the measure pass wrote it.  Then the events of a clean
+// group leave the rest (key string field n_strings + 1, an empty set) and are
+// replayed by chain_event; the confirmed heads are counted per buffer.
+__global__ __launch_bounds__(64 * kChainWaves) void batch_chain_replay_kernel(BatchChainParams c,
+                                                                              uint32_t waves) {
+  __shared__ uint32_t share[kChainWaves][4 * kChainLdsEntries];
+  const MatchParams& p = c.b.h.m;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t n = (uint32_t)p.n;   // (at most kMatchMaxRecords)
+  const uint32_t groups = min(uni(c.counts[0]), n);
+  const ChainSink sink{c.item_keys, c.item_index, c.counts + 1};
+  for (uint32_t g = blockIdx.x * kChainWaves + wave; g < groups; g += waves) {
+    const uint32_t begin = uni(c.gbegin[g]);
+    if (begin >= n) continue;   // (never)
+    // (a key is a chain or n_chains: 32 bits)
+    const uint32_t chain = uni((uint32_t)c.sorted_keys[begin]);
+    const uint32_t k = uni(c.b.buf[c.sorted_index[begin]]);
+    if (chain >= c.t.n_chains || k >= c.b.nbuf) continue;   // (never)
+    const uint32_t s0 = uni(c.t.chain_off[chain]);
+    const uint32_t levels = uni(c.t.chain_off[chain + 1]) - s0;   // (2 .. kChainMaxLevels)
+    uint32_t lstr = 0, lbase = 0, llen = 0, cap = 0;
+    int32_t lgmin = 0, lgmax = 0;
+    if (lane < levels) {
+      lstr = c.t.chain_strs[s0 + lane];
+      lgmin = c.t.gap_min[lstr];
+      lgmax = c.t.gap_max[lstr];
+    }
+    uint32_t end = begin;
+    bool dirty = false;
+    for (uint32_t eb = begin; !dirty; eb += 64) {
+      const uint32_t i = eb + lane;
+      bool in = false;
+      uint32_t lv = 0;
+      if (i < n && c.sorted_keys[i] == chain) {
+        const uint32_t r = c.sorted_index[i];
+        in = c.b.buf[r] == k;
+        lv = c.ev_level[r];
+      }
+      const uint64_t out = ~__ballot(in);
+      const uint32_t cnt = out == 0 ? 64u : (uint32_t)__builtin_ctzll(out);
+      const bool v = lane < cnt;
+      dirty = __ballot(v && lv == kChainDirtyMaker) != 0;
+      for (uint32_t l = 0; l + 1 < levels; ++l) {   // (the tail keeps no list)
+        const uint32_t here = (uint32_t)__popcll(__ballot(v && lv == l));
+        if (lane == l) cap += here;
+      }
+      end = eb + cnt;
+      if (cnt < 64) break;
+    }
+    if (dirty) continue;
+    const uint32_t upto = wave_prefix(cap);
+    Lists L;
+    if (lane_of(upto, 63) <= kChainLdsEntries) {
+      lbase = upto - cap;
+      L.off = share[wave];
+    } else {
+      lbase = begin + upto - cap;   // (upto <= end - begin: inside the run's slots)
+      L.off = c.lists;
+    }
+    const uint64_t stride = L.off == c.lists ? p.n : kChainLdsEntries;
+    L.len = L.off + stride;
+    L.cl = L.len + stride;
+    L.rec = L.cl + stride;
+    const uint32_t head = lane_of(lstr, 0);
+    uint32_t confirmed = 0;
+    for (uint32_t eb = begin; eb < end; eb += 64) {
+      const uint32_t cnt = min(64u, end - eb);
+      uint32_t erec = 0, elvl = 0, eoff = 0, elen = 0;
+      if (lane < cnt) {
+        erec = c.sorted_index[eb + lane];
+        elvl = c.ev_level[erec];
+        eoff = c.ev_offset[erec];
+        elen = c.ev_length[erec];
+        p.keys[erec] = (uint64_t)(p.n_strings + 1) << 32 | (p.keys[erec] & 0xFFFFFFFFull);
+        c.b.h.sets[erec] = HexSet{0ull, 0u, 0u};
+      }
+      for (uint32_t j = 0; j < cnt; ++j)
+        chain_event(L, levels, head, lane_of(elvl, j), lane_of(eoff, j), lane_of(elen, j),
+                    lane_of(erec, j), lbase, llen, lgmin, lgmax, p, sink, confirmed);
+    }
+    if (lane == 0 && confirmed != 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(c.buf_items + k), (unsigned long long)confirmed);
+  }
+}
+
+// The per-wave rest counts again, as the measure pass wrote them, now that the
+// clean groups' events have left the rest.
+__global__ __launch_bounds__(256) void batch_chain_recount_kernel(BatchChainParams c) {
+  const MatchParams& p = c.b.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool rest = r < p.n && (uint32_t)(p.keys[r] >> 32) == p.n_strings;
+  const uint64_t mask = __ballot(rest);
+  if ((threadIdx.x & 63u) == 0 && r < p.n) p.block_off[r / kGroup] = (uint64_t)__popcll(mask);
+}
+
+// One lane per k in [0, nbuf]: buffer k's slots in the sorted item arrays begin
+// behind the records' items AND the chain items of the buffers before it.
+__global__ __launch_bounds__(256) void batch_chain_item_offsets_kernel(BatchChainParams c) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > c.b.nbuf) return;
+  c.b.item_off[k] += c.buf_chunk[k / kChunkGroups] + c.buf_items[k];
 }
 
 inline dim3 chain_grid(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
@@ -428,6 +662,33 @@ hipError_t launch_chain_replay(const ChainParams& c, uint32_t waves, hipStream_t
   const uint32_t blocks = (std::min(waves, c.t.n_chains) + kChainWaves - 1) / kChainWaves;
   hipLaunchKernelGGL(chain_replay_kernel, dim3(blocks), dim3(64 * kChainWaves), 0, s, c,
                      blocks * kChainWaves);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_chain_events(const BatchChainParams& c, hipStream_t s) {
+  const uint64_t n = c.b.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords || c.t.n_chains == 0 || c.b.nbuf == 0) return hipErrorInvalidValue;
+  // (a kernel, not memsets: the stage may be recorded into a graph)
+  hipLaunchKernelGGL(batch_chain_clear_kernel, chain_grid((uint64_t)c.b.nbuf + 1), dim3(256), 0, s, c);
+  hipLaunchKernelGGL(batch_chain_events_kernel, chain_grid(n), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_chain_replay(const BatchChainParams& c, uint32_t waves, hipStream_t s) {
+  const uint64_t n = c.b.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords || c.t.n_chains == 0 || waves == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_chain_groups_kernel, chain_grid(n), dim3(256), 0, s, c);
+  // (at most a wave per record: there are no more groups than that)
+  const uint32_t blocks = ((uint32_t)std::min<uint64_t>(waves, n) + kChainWaves - 1) / kChainWaves;
+  hipLaunchKernelGGL(batch_chain_replay_kernel, dim3(blocks), dim3(64 * kChainWaves), 0, s, c,
+                     blocks * kChainWaves);
+  hipLaunchKernelGGL(batch_chain_recount_kernel, chain_grid(n), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_chain_item_offsets(const BatchChainParams& c, hipStream_t s) {
+  hipLaunchKernelGGL(batch_chain_item_offsets_kernel, chain_grid((uint64_t)c.b.nbuf + 1), dim3(256), 0,
+                     s, c);
   return hipGetLastError();
 }
 

@@ -332,4 +332,49 @@ hipError_t launch_chain_events(const ChainParams& c, hipStream_t s);
 // items and their lengths left in m.meas at the head's record.
 hipError_t launch_chain_replay(const ChainParams& c, uint32_t waves, hipStream_t s);
 
+// ---- The batch's chains (yr_amd_scanner_set_batch_chains) ----
+// A chain is replayed per (buffer, chain) GROUP, its events measured inside
+// their own buffer.  Nothing here is sized by nbuf x n_chains or nbuf x
+// n_strings: the events and the dirty-makers (records that are not exactly one
+// event) get their chain as sort key, batch_match_sort orders them by (buffer,
+// chain) -- stable, so each group is one contiguous run in record order -- and
+// the groups are found in that stream.  A group's dirtiness is read off its
+// own run, its lists live in its own slots [begin, end) of `lists` (a list
+// holds at most its level's events), and the confirmed heads are counted per
+// buffer so that the items' CSR can account for them.
+// A struct of its own: ChainParams and BatchHexParams are kernel arguments of
+// the kernels above, which stay what they are.
+constexpr uint32_t kChainDirtyMaker = 0xFFFFFFFFu;   // ev_level of a dirty-maker
+struct BatchChainParams {
+  BatchHexParams b;             // the measure pass's, + buf; h.m.keys / h.sets / h.m.block_off are
+                                //   rewritten for the consumed records as in ChainParams
+  ChainTables t;
+  uint32_t* ev_level;           // [n] by record: the event {level, local offset, length},
+  uint32_t* ev_offset;          //   level kChainDirtyMaker: no event, its group is dirty
+  uint32_t* ev_length;
+  uint64_t* skeys;              // [n] the sort's keys: the chain of an event or dirty-maker,
+  uint32_t* sindex;             //   else n_chains (values: the record)
+  const uint64_t* sorted_keys;  // after the stable sort by (buffer, chain)
+  const uint32_t* sorted_index;
+  uint32_t* gbegin;             // [n] the group list: each group's first sorted slot
+  uint32_t* counts;             // {groups, items appended}
+  uint32_t* lists;              // [4][n] the unconfirmed lists past the LDS share
+  uint64_t* item_keys;          // [n] the confirmed heads: string << 32 | local offset
+  uint32_t* item_index;         // [n] the head's record
+  uint64_t* buf_items;          // [nbuf + 1] chain items per buffer -> offsets within chunks
+  uint64_t* buf_chunk;          // [verify_chunks(nbuf * kGroup) + 1] (launch_block_offsets)
+};
+
+// Clear; one lane per record (behind the batch measure pass): the event or the
+// dirty-maker, + skeys / sindex.
+hipError_t launch_batch_chain_events(const BatchChainParams& c, hipStream_t s);
+// (skeys sorted by batch_match_sort) the group list; one wave per group: a
+// clean group's events leave the rest and are replayed, the confirmed heads
+// appended as items and counted into buf_items; then the per-wave rest counts
+// again.  Ahead of the rest's offsets.
+hipError_t launch_batch_chain_replay(const BatchChainParams& c, uint32_t waves, hipStream_t s);
+// (buf_items scanned, item_off written) item_off[k] += the chain items of the
+// buffers below k.
+hipError_t launch_batch_chain_item_offsets(const BatchChainParams& c, hipStream_t s);
+
 }  // namespace yamd

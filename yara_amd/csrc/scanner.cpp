@@ -282,6 +282,9 @@ struct yr_amd_scanner {
   bool chains = false;
   uint64_t* d_chain_ws = nullptr;
   size_t chain_ws_cap = 0;
+  // the batch's own setting (yr_amd_scanner_set_batch_chains; matches.h
+  // BatchChainParams): the same workspace, laid out by match_batch_device_hex
+  bool batch_chains = false;
 
   // batched scans (yr_amd_scan_batch_device): the last scan was a batch's arena
   // scan / its stream has been cut into the buffers' (yr_amd_scan_batch_result)
@@ -2582,12 +2585,21 @@ namespace {
 // waits, as match_device_hex: the item count sizes the sort's workspace.  The
 // offsets go to s->h_mrest_off (first wait) and s->h_match_off (second; zeros
 // without items).
+// chains: the records of settled chains become events, grouped by (buffer,
+// chain) and replayed a wave per group (matches.h BatchChainParams), all of it
+// queued ahead of the first wait -- the same two waits.
+inline uint32_t batch_chain_waves(const yr_amd_tables* t) {
+  return 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
+}
+
 int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n,
-                           uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni) {
+                           uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni, bool chains) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
   const size_t noff = (size_t)nbuf + 1;
-  int r = ensure_match_workspace(s, 1);   // (the pinned totals; the items' arrays grow below)
+  // (the pinned totals; the items' arrays grow below.  With chains the events'
+  // sort by (buffer, chain) runs in the items' arrays before the items exist.)
+  int r = ensure_match_workspace(s, chains ? n : 1);
   if (!r) r = grow_geo(s->d_hkeys, s->hkeys_cap, n);
   if (!r) r = grow_geo(s->d_hmeas, s->hmeas_cap, n);
   if (!r) r = grow_geo(s->d_hsets, s->hsets_cap, n);
@@ -2631,6 +2643,33 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   rp.nbuf = nbuf;
   rp.rest_off = s->d_moff + noff;
   const KeptLists none{{0, 0, 0, 0}};
+  BatchChainParams c{};
+  const uint32_t n_chains = t->d_chain.n_chains;
+  int chain_bits = 1;   // the sort key's values: a chain, or n_chains for "neither"
+  if (chains) {
+    while (chain_bits < 32 && (n_chains >> chain_bits) != 0) ++chain_bits;
+    // the workspace, by the record count and nbuf alone: the 64-bit arrays
+    // first, then the 32-bit ones
+    const size_t buf_chunks = verify_chunks((uint64_t)nbuf * kGroup) + 1;
+    const size_t words64 = n + noff + buf_chunks;
+    const size_t words32 = 9 * n + 2;
+    r = grow_geo(s->d_chain_ws, s->chain_ws_cap, words64 + (words32 + 1) / 2);
+    if (r) return r;
+    c.t = t->d_chain;
+    c.item_keys = s->d_chain_ws;
+    c.buf_items = c.item_keys + n;
+    c.buf_chunk = c.buf_items + noff;
+    uint32_t* w = reinterpret_cast<uint32_t*>(s->d_chain_ws + words64);
+    c.ev_level = w;
+    c.ev_offset = w + n;
+    c.ev_length = w + 2 * n;
+    c.lists = w + 3 * n;
+    c.item_index = w + 7 * n;
+    c.gbegin = w + 8 * n;
+    c.counts = w + 9 * n;
+    c.skeys = s->d_mkeys;
+    c.sindex = s->d_mindex;
+  }
   // The batch's wave-wide path (BatchHexWideParams), as in match_device_hex: the
   // records given up on for width are queued with their buffers and measured one
   // wave each, the queue's length not waited for; should it pass the capacity,
@@ -2670,6 +2709,20 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
       HIP_TRY(launch_batch_hex_wide_measure(bw, wide_waves, s->stream));
     else
       HIP_TRY(launch_batch_hex_measure(b, s->stream));
+    if (chains) {
+      // the events; by (buffer, chain), in record order; the groups replayed,
+      // the clean ones' events out of the rest's counts
+      c.b = b;
+      HIP_TRY(launch_batch_chain_events(c, s->stream));
+      uint64_t* const ckeys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
+      uint32_t* const cindex[2] = {s->d_mindex, s->d_mindex + s->match_cap};
+      int csorted = 0;
+      HIP_TRY(batch_match_sort(ckeys, cindex, n, chain_bits, 0, b.buf, nbuf, s->d_mhist,
+                               s->d_mhchunk, s->d_mhsum + 2, s->stream, &csorted));
+      c.sorted_keys = ckeys[csorted];
+      c.sorted_index = cindex[csorted];
+      HIP_TRY(launch_batch_chain_replay(c, batch_chain_waves(t), s->stream));
+    }
     HIP_TRY(launch_block_offsets(m.block_off, m.chunk_off, n, s->d_mhsum, nullptr, none, s->stream));
     HIP_TRY(launch_block_offsets(b.h.iblock_off, b.h.ichunk_off, n, s->d_mhsum + 3, nullptr, none,
                                  s->stream));
@@ -2679,6 +2732,11 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
       HIP_TRY(launch_batch_hex_wide_offsets(bw, s->stream));
     else
       HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
+    if (chains) {   // the chain items per buffer, scanned, into the items' CSR
+      HIP_TRY(launch_block_offsets(c.buf_items, c.buf_chunk, (uint64_t)nbuf * kGroup, s->d_mhsum + 5,
+                                   nullptr, none, s->stream));
+      HIP_TRY(launch_batch_chain_item_offsets(c, s->stream));
+    }
     HIP_TRY(hipMemcpyAsync(s->h_mrest_off.data(), rp.rest_off, noff * sizeof(uint64_t),
                            hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -2687,13 +2745,17 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
     if (!wide || queued <= bw.w.qcap) break;
   }
   *nr = s->h_msum[0];
-  const uint64_t items = s->h_msum[3];
-  *ni = items;
+  const uint64_t hex_items = s->h_msum[3];
   *nm = 0;
   // (a record of the wave-wide path is up to YR_RE_SCAN_LIMIT + 1 items)
-  if (*nr > n || items > (wide ? (uint64_t)kReScanLimit + 1 : 64) * (n - *nr) ||
+  if (*nr > n || hex_items > (wide ? (uint64_t)kReScanLimit + 1 : 64) * (n - *nr) ||
       s->h_mrest_off[nbuf] != *nr)
     return YR_AMD_INTERNAL_FATAL_ERROR;
+  // the confirmed heads: at most one per record that left the rest
+  const uint64_t chain_items = chains ? s->h_msum[5] : 0;
+  if (chain_items > n - *nr) return YR_AMD_INTERNAL_FATAL_ERROR;
+  const uint64_t items = hex_items + chain_items;
+  *ni = items;
   if (debug_level() >= 1 && wide)
     fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_batch_device()\n",
             (unsigned long long)n, (unsigned long long)queued);
@@ -2723,6 +2785,15 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
     HIP_TRY(launch_hex_wide_expand(bw.w, wide_waves, s->stream));
   } else {
     HIP_TRY(launch_hex_expand(b.h, s->stream));
+  }
+  if (chain_items > 0) {
+    // behind the records' items, in confirm order; the sort by (buffer, string,
+    // offset) takes each to its buffer's slots -- item_off counts them -- and is
+    // stable, so of two confirmations of one (head, offset) the first stays first
+    HIP_TRY(hipMemcpyAsync(b.h.ikeys + hex_items, c.item_keys, chain_items * sizeof(uint64_t),
+                           hipMemcpyDeviceToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(b.h.iindex + hex_items, c.item_index, chain_items * sizeof(uint32_t),
+                           hipMemcpyDeviceToDevice, s->stream));
   }
   int sorted = 0;
   HIP_TRY(batch_match_sort(keys, index, items, lo_bits, hi_bits, b.buf, nbuf, s->d_mhist,
@@ -2758,6 +2829,18 @@ int yr_amd_scanner_set_batch_hex_wide(yr_amd_scanner* s, int enable) {
   return YR_AMD_SUCCESS;
 }
 
+int yr_amd_scanner_set_batch_chains(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->batch_chains = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
+int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* s, uint32_t* waves) {
+  if (s == nullptr || waves == nullptr) return YR_AMD_INVALID_ARGUMENT;
+  *waves = batch_chain_waves(s->tables);
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
                               const yr_amd_match_rec** d_matches, const uint64_t** match_off,
                               const yr_amd_verify_rec** d_rest, const uint64_t** rest_off) {
@@ -2768,6 +2851,10 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   // the hex class interprets the strings' programs (yr_amd_tables_set_re_code)
   const bool hex = (s->batch_match_classes & kMatchHex) != 0;
   if (hex && t->d_re_code == nullptr) return YR_AMD_INVALID_ARGUMENT;
+  // chained strings (yr_amd_scanner_set_batch_chains): the events are assembled
+  // behind the records' measure pass, so chains take the hex driver
+  if (s->batch_chains && !t->has_chains) return YR_AMD_INVALID_ARGUMENT;
+  const bool chains = s->batch_chains && t->d_chain.n_chains > 0;
   const yr_amd_verify_rec* d_rec = nullptr;
   const uint64_t* rec_off = nullptr;
   int r = yr_amd_verify_batch_device(s, bases, &d_rec, &rec_off);
@@ -2778,8 +2865,8 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   s->h_match_off.assign((size_t)nbuf + 1, 0);
   s->h_mrest_off.assign((size_t)nbuf + 1, 0);
   uint64_t nm = 0, nr = 0, ni = 0;
-  if (n > 0 && hex) {
-    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni);
+  if (n > 0 && (hex || chains)) {
+    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni, chains);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n, nbuf);
@@ -2844,7 +2931,7 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
     if (nr > n || nm > n - nr || s->h_match_off[nbuf] != nm || s->h_mrest_off[nbuf] != nr)
       return YR_AMD_INTERNAL_FATAL_ERROR;
   }
-  if (debug_level() >= 1 && hex)
+  if (debug_level() >= 1 && (hex || chains))
     fprintf(stderr,
             "- %u buffers, %llu verify calls -> %llu items -> %llu matches, %llu calls left // "
             "yr_amd_match_batch_device()\n",
@@ -2857,7 +2944,8 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
             nbuf, (unsigned long long)n, (unsigned long long)nm, (unsigned long long)nr);
   if (d_matches) *d_matches = reinterpret_cast<const yr_amd_match_rec*>(s->d_mout);
   if (match_off) *match_off = s->h_match_off.data();
-  if (d_rest) *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex ? s->d_hrest : s->d_mrest);
+  if (d_rest)
+    *d_rest = reinterpret_cast<const yr_amd_verify_rec*>(hex || chains ? s->d_hrest : s->d_mrest);
   if (rest_off) *rest_off = s->h_mrest_off.data();
   return YR_AMD_SUCCESS;
 }
@@ -2869,6 +2957,7 @@ int yr_amd_scan_batch_matches(yr_amd_scanner* s, const uint8_t* const* data, con
   if (s == nullptr || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
   if ((s->batch_match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
     return YR_AMD_INVALID_ARGUMENT;
+  if (s->batch_chains && !s->tables->has_chains) return YR_AMD_INVALID_ARGUMENT;
   int r = scan_batch_host(s, data, sizes, n);
   const yr_amd_match_rec* d_m = nullptr;
   const yr_amd_verify_rec* d_r = nullptr;
