@@ -697,6 +697,73 @@ int yr_amd_tables_chain_strings(
 int yr_amd_scanner_set_chains(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
 
 /*
+ * Alternation strings: the strings whose programs are loop-free yr_re_exec
+ * programs -- hex strings with alternatives, { E8 ?? ?? ?? ?? ( 5B | 5D ) C3 },
+ * and regexps without * and +, /(cat|dog|bird)house/, /ab[0-9]c/ -- settled by
+ * the match stage too.  A setting of its own: the classes of
+ * yr_amd_scanner_set_match_classes and yr_amd_tables_match_strings are
+ * unchanged, and bits 4 and 8 are still refused there.
+ *
+ * yr_amd_tables_alternation_strings: out[k] = 1 iff string k is an alternation
+ * string.  Host code with the preconditions of yr_amd_tables_match_strings,
+ * plus the programs (yr_amd_tables_set_re_code, or a .yarc file -- host-only
+ * tables loaded from one carry them too); YR_AMD_INVALID_ARGUMENT otherwise.
+ * String k is one when
+ *   1. ASCII is set and none of LITERAL, FAST_REGEXP, CHAIN_PART, CHAIN_TAIL,
+ *      WIDE, NO_CASE, FULL_WORD, XOR, BASE64, BASE64_WIDE (DOT_ALL and
+ *      GREEDY_REGEXP either way);
+ *   2. it has a pool entry, every pool entry of it has a forward program, and
+ *      each program (forward, and backward where present) is LOOP-FREE: every
+ *      instruction reachable from its entry is one of ANY, LITERAL,
+ *      NOT_LITERAL, MASKED_LITERAL, MASKED_NOT_LITERAL, CLASS, \w \W \s \S \d
+ *      \D, REPEAT_ANY_GREEDY / _UNGREEDY, SPLIT_A, SPLIT_B, JUMP, MATCH; every
+ *      SPLIT / JUMP target lies above the instruction's own address; at most 64
+ *      instructions are reachable; no split id names two instructions;
+ *   3. an upper bound on the fibers yr_re_exec can hold while running the
+ *      program is below RE_MAX_FIBERS (1024), so that stock libyara cannot
+ *      fail with ERROR_TOO_MANY_RE_FIBERS on it (DESIGN.md 18.8 has the bound).
+ *
+ * yr_amd_scanner_set_alternations(1): yr_amd_match_device and
+ * yr_amd_scan_block_matches also settle the records of alternation strings,
+ * as _yr_scan_verify_re_match (scan.c:778-885) does with yr_re_exec
+ * (re.c:1693-2068): the forward length F is the bytes_matched of the
+ * HIGHEST-PRIORITY path that reaches MATCH (SPLIT_A prefers the next
+ * instruction, SPLIT_B its target, REPEAT_ANY_UNGREEDY the fewest repetitions,
+ * _GREEDY the most) -- not the shortest one; every distinct bytes_matched B of
+ * the backward program at MATCH is a match {offset - B, B + F}, without a
+ * backward program {offset, F} unless F is 0; xor_key 0.  Across records the
+ * rule of the hex class holds: one entry per (string, offset), the first
+ * record in record order supplying length and pool_index.  A record stays in
+ * the rest, never out as a guess, when no path reaches MATCH, when a run would
+ * have to read input byte 64 or later (bytes_matched lives in a 64-position
+ * window; a forward length of exactly 64 is still settled, a backward one is
+ * not), or when, after yr_amd_scan_window, a byte either run may read lies
+ * outside the window.  A chain with an alternation part stays unsettled.
+ * Read by yr_amd_match_device and yr_amd_scan_block_matches only, and only
+ * when the scanner's classes include YR_AMD_MATCH_HEX; the batch calls never
+ * read it.  With the setting on and tables without programs the two calls
+ * return YR_AMD_INVALID_ARGUMENT (as they do for the hex class); with it off
+ * they launch what they launched before.  Should the records outgrow the
+ * device queue, the first wait sees it, the queue grows and the measure pass
+ * runs again.  NULL scanner or a value other than 0/1:
+ * YR_AMD_INVALID_ARGUMENT.
+ *
+ * Host-only tables (device < 0) get their programs from
+ * yr_amd_tables_load_yarc, which therefore fails where attaching them fails
+ * (a program outside the code blob: YR_AMD_INVALID_ARGUMENT).  The library
+ * also exports two symbols that this header does not declare and that are no
+ * part of the interface, as yr_amd__re_fiber_safe is not:
+ * yr_amd__tables_set_host_programs (what load_yarc calls for host-only
+ * tables; the Python wrapper's from_npz(device=-1, strings=True) uses it) and
+ * yr_amd__alternation_program (conditions 2 and 3 on one program, for tests).
+ */
+int yr_amd_tables_alternation_strings(
+    const yr_amd_tables* tables,
+    uint8_t* out,
+    uint32_t n_strings);
+int yr_amd_scanner_set_alternations(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
+
+/*
  * ---- Batched scans: many independent buffers in one launch ----
  *
  * Every call above takes one block and pays its fixed cost -- a scan launch in

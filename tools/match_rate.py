@@ -36,6 +36,17 @@ of the hexwide fixture's `back` string ({ B5 [0-100] B1 B2 B3 B4 }, 1 to 100
 starts each) under that fixture's tables: every record is wide, the difference
 over the records is the time per wide record.  The D2H of the rest with the
 setting off is again the lower bound of what a caller does without it.
+
+    python tools/match_rate.py --alternations [--gib 1] [--reps 10] [--parent-tree DIR --rounds 5]
+                               [--out profiles/alternation_match_rates.json]
+
+Alternation strings (yr_amd_scanner_set_alternations), classes LITERAL | HEX, on
+rx's planted input: the setting off and on alternating in one process, medians
+with min..max, records -> matches and rest for both.  With --parent-tree the
+setting is left off and the same calls are timed on this tree's library and on
+another build's (the parent commit's), one child process each, alternating
+--rounds times: the idle cost of the change next to the run-to-run spread the
+same runs show.
 """
 import argparse
 import json
@@ -45,7 +56,8 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+# (YARA_AMD_PACKAGE_ROOT: another build's yara_amd package with its library, --parent-tree's child)
+sys.path.insert(0, os.environ.get("YARA_AMD_PACKAGE_ROOT") or REPO)
 
 
 def hex_leg(a):
@@ -213,6 +225,101 @@ def hex_wide_leg(a):
             f.write("\n")
 
 
+def alternations_leg(a):
+    """yr_amd_match_device on rx's planted input resident in HBM, classes LITERAL | HEX, the
+    alternation setting off and on, alternating.  With --parent-tree: the setting OFF on this
+    tree's library and on another build's (the parent commit's), one child process each,
+    alternating, a.rounds times -- the idle cost of the change against its run-to-run spread."""
+    import ctypes
+    import subprocess
+    import numpy as np
+    med = lambda v: round(statistics.median(v), 4)   # noqa: E731
+    span = lambda v: [round(min(v), 4), round(max(v), 4)]   # noqa: E731
+    if a.parent_tree and not a.child:
+        out = {"bytes": int(a.gib * (1 << 30)), "reps": a.reps, "rounds": a.rounds, "runs": []}
+        sides = {"this": None, "parent": os.path.abspath(a.parent_tree)}
+        meds = {k: [] for k in sides}
+        for _ in range(a.rounds):
+            for side, lib in sides.items():
+                env = dict(os.environ)
+                if lib:
+                    env["YARA_AMD_PACKAGE_ROOT"] = lib
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--alternations",
+                                    "--child", "--gib", str(a.gib), "--reps", str(a.reps)],
+                                   env=env, capture_output=True, text=True, timeout=300)
+                if r.returncode != 0:   # (nothing more is started on the device)
+                    sys.exit("child (%s) failed with %d:\n%s" % (side, r.returncode, r.stderr[-2000:]))
+                ms = json.loads(r.stdout.strip().splitlines()[-1])["off_ms"]
+                meds[side].append(ms)
+                out["runs"].append({"side": side, "off_ms": ms})
+        out["idle"] = {k: {"median_ms": med(v), "min_max_ms": span(v)} for k, v in meds.items()}
+        out["idle"]["this_over_parent"] = round(med(meds["this"]) / med(meds["parent"]), 4)
+        out["idle"]["spread"] = {k: round((max(v) - min(v)) / med(v), 4) for k, v in meds.items()}
+        print(json.dumps(out["idle"]), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+                f.write("\n")
+        return
+    import torch
+    import yara_amd
+    from yara_amd import _lib
+    sys.path[:0] = [os.path.join(REPO, "tests", "golden")]
+    sys.path.append(REPO)   # (oracle; behind a --parent-tree package root)
+    import oracle
+    import planted
+    n = int(a.gib * (1 << 30))
+    golden = os.path.join(REPO, "tests", "golden")
+    host = planted.rx_buffer(oracle.xorshift, n, 19)   # (rx_1M's generator at this size)
+    stream = torch.cuda.Stream()
+    buf = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+    buf[:n] = torch.from_numpy(host).cuda()
+    torch.cuda.synchronize()
+    sc = yara_amd.Scanner(yara_amd.Tables.from_npz(os.path.join(golden, "tables", "rx.npz"),
+                                                   strings=True), stream=stream.cuda_stream)
+    sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+    sc.scan_device(buf.data_ptr(), n)
+    sc.device_result()
+
+    def stage(on):   # (ms, n_matches, n_rest): the device call alone
+        if on is not None:
+            sc.set_alternations(on)
+        pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
+        nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        _lib.check("yr_amd_match_device", _lib.lib().yr_amd_match_device(
+            sc._h, 0, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr), ctypes.byref(nr)))
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1), nm.value, nr.value
+
+    if a.child:   # the setting is never touched: the same calls on either library
+        for _ in range(3):
+            stage(None)
+        print(json.dumps({"off_ms": med([stage(None)[0] for _ in range(a.reps)])}), flush=True)
+        return
+    for _ in range(2):   # warm-up: buffers grown, clocks up
+        stage(False)
+        stage(True)
+    off, on = [], []
+    for _ in range(a.reps):   # interleaved
+        ms, m_off, r_off = stage(False)
+        off.append(ms)
+        ms, m_on, r_on = stage(True)
+        on.append(ms)
+    out = {"bytes": n, "reps": a.reps, "classes": "LITERAL | HEX", "input": "rx planted",
+           "records": sc.verify_device(0)[1],
+           "off": {"matches": m_off, "rest": r_off, "match_device_ms": med(off), "min_max_ms": span(off)},
+           "on": {"matches": m_on, "rest": r_on, "match_device_ms": med(on), "min_max_ms": span(on)},
+           "added_ms": round(med(on) - med(off), 4), "alternation_records": r_off - r_on}
+    print(json.dumps(out), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="C,short")
@@ -224,7 +331,17 @@ def main():
     ap.add_argument("--hex-wide", action="store_true",
                     help="the wave-wide path: the setting off and on, on C's planted input and "
                          "on planted copies of the hexwide fixture's `back` string")
+    ap.add_argument("--alternations", action="store_true",
+                    help="alternation strings: the setting off and on, on rx's planted input")
+    ap.add_argument("--parent-tree", default=None,
+                    help="with --alternations: a directory holding another build's yara_amd package "
+                         "(the parent commit's, with its library) to time the setting off against, "
+                         "alternating child processes")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.alternations:
+        return alternations_leg(a)
     if a.hex_wide:
         return hex_wide_leg(a)
     if a.hex:

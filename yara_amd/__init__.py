@@ -123,6 +123,11 @@ class Tables:
         if strings and device < 0:
             # host-only tables carry no device strings: the flags alone
             t.set_string_flags(z["str_flags"])
+            if regex and "re_kind" in z:
+                # ... and the programs, all that alternation_strings reads of them
+                fl = np.where(z["re_kind"] != 0, z["re_fwd_len"], 0)
+                t._set_host_programs(z["pool_string"], z["re_fwd_off"], fl, z["re_bwd_off"],
+                                     z["re_bwd_len"], z["re_code"])
         elif strings:
             offs = z["str_offsets"]
             t.set_strings(z["pool_string"], z["str_flags"], np.diff(offs), z["str_fixed_offset"],
@@ -155,6 +160,33 @@ class Tables:
         _lib.check("yr_amd_tables_chain_strings", _lib.lib().yr_amd_tables_chain_strings(
             self._h, classes, out.ctypes.data_as(_lib._u8p), n))
         return out[:n].astype(bool)
+
+    def alternation_strings(self):
+        """bool[n_strings]: the strings ``Scanner.set_alternations`` settles
+        (yr_amd_tables_alternation_strings): loop-free yr_re_exec programs --
+        hex strings with alternatives, regexps without * and +.  The tables
+        need their programs (set_re_code, from_npz with strings, a .yarc)."""
+        n = self.string_count()
+        out = np.zeros(max(n, 1), np.uint8)
+        _lib.check("yr_amd_tables_alternation_strings",
+                   _lib.lib().yr_amd_tables_alternation_strings(
+                       self._h, out.ctypes.data_as(_lib._u8p), n))
+        return out[:n].astype(bool)
+
+    def _set_host_programs(self, pool_string, fwd_off, fwd_len, bwd_off, bwd_len, code):
+        # host-only tables: the programs for alternation_strings
+        arrs = [_arr(a, np.uint32) for a in (pool_string, fwd_off, fwd_len, bwd_off, bwd_len)]
+        n = arrs[0].size
+        arrs = [a if a.size else np.zeros(1, np.uint32) for a in arrs]
+        blob = _arr(code, np.uint8) if len(code) else np.zeros(1, np.uint8)
+        fn = _lib.lib().yr_amd__tables_set_host_programs   # (not part of the declared ABI)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, _lib._u32p, ctypes.c_uint32] + [_lib._u32p] * 4 + \
+            [_lib._u8p, ctypes.c_uint64]
+        _lib.check("yr_amd__tables_set_host_programs", fn(
+            self._h, arrs[0].ctypes.data_as(_lib._u32p), n,
+            *[a.ctypes.data_as(_lib._u32p) for a in arrs[1:]], blob.ctypes.data_as(_lib._u8p),
+            len(code)))
 
     def set_re_code(self, fwd_off, fwd_len, bwd_off, bwd_len, code):
         """Attach fast-exec RE programs (yr_amd_tables_set_re_code)."""
@@ -298,6 +330,7 @@ class Scanner:
         self._batch_hex_wide = False   # set_batch_hex_wide
         self._batch_chains = False   # set_batch_chains
         self._chains = False   # set_chains
+        self._alternations = False   # set_alternations
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -390,11 +423,23 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_chains(self._h, int(enable)))
         self._chains = bool(enable)
 
-    def _with_hex(self, hex, call, wide=False, chains=False):
+    def set_alternations(self, enable: bool):
+        """Settle alternation strings too (yr_amd_scanner_set_alternations):
+        the strings ``Tables.alternation_strings`` names, with the forward
+        length of yr_re_exec's highest-priority path.  Read only while the
+        classes include MATCH_HEX; the batch calls never read it."""
+        _lib.check("yr_amd_scanner_set_alternations",
+                   _lib.lib().yr_amd_scanner_set_alternations(self._h, int(enable)))
+        self._alternations = bool(enable)
+
+    def _with_hex(self, hex, call, wide=False, chains=False, alternations=False):
         # hex=True: this call with the hex class added (wide=True: and the
-        # wave-wide path on; chains=True: and chained strings settled), the
-        # scanner's settings restored
+        # wave-wide path on; chains=True: and chained strings settled;
+        # alternations=True: and alternation strings settled), the scanner's
+        # settings restored
         was, was_wide = self._classes, self._hex_wide
+        if not alternations or self._alternations:
+            alternations = False
         if not hex or (was & MATCH_HEX):
             hex = False
         if not wide or was_wide:
@@ -407,9 +452,13 @@ class Scanner:
             self.set_hex_wide(True)
         if chains:
             self.set_chains(True)
+        if alternations:
+            self.set_alternations(True)
         try:
             return call()
         finally:
+            if alternations:
+                self.set_alternations(False)
             if chains:
                 self.set_chains(False)
             if wide:
@@ -480,7 +529,7 @@ class Scanner:
                 self.set_batch_match_classes(was)
 
     def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False,
-                     chains: bool = False):
+                     chains: bool = False, alternations: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
         copied to the host: ``matches`` {offset, string, length, xor_key,
         pool_index}, one per distinct (string, offset) of the final strings
@@ -496,8 +545,11 @@ class Scanner:
         implies nothing, it goes with ``hex=True`` or a scanner whose classes
         hold MATCH_HEX.  ``chains=True`` settles the chained strings for this
         call (set_chains): the heads' matches join ``matches``, the events of
-        settled, clean chains leave ``rest``."""
-        return self._with_hex(hex, lambda: self._match_device(data_base), wide, chains)
+        settled, clean chains leave ``rest``.  ``alternations=True`` settles
+        the alternation strings for this call (set_alternations;
+        Tables.alternation_strings); like ``wide`` it goes with the hex class."""
+        return self._with_hex(hex, lambda: self._match_device(data_base), wide, chains,
+                              alternations)
 
     def _match_device(self, data_base):
         from ._hip import memcpy
@@ -515,12 +567,13 @@ class Scanner:
         return matches, rest
 
     def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False,
-                       wide: bool = False, chains: bool = False):
+                       wide: bool = False, chains: bool = False, alternations: bool = False):
         """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
         see match_device.  For the final strings ``matches`` is what stock
         libyara's match lists hold after scanning this block alone; the blocks
         of one scan merge with ``merge_matches``."""
-        return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide, chains)
+        return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide, chains,
+                              alternations)
 
     def _string_matches(self, data, data_base):
         d = _arr(data, np.uint8)

@@ -266,6 +266,67 @@ hipError_t launch_batch_hex_wide_measure(const BatchHexWideParams& p, uint32_t w
 // item_off from the scanned item counts (iblock_off / ichunk_off) and istart.
 hipError_t launch_batch_hex_wide_offsets(const BatchHexWideParams& p, hipStream_t s);
 
+// The pieces of launch_hex_wide_measure one by one, for a driver that runs a
+// measure pass of its own between them (alternations.hip): 0 the queue's
+// length cleared, 1 one wave per queued record, 2 the recount.
+hipError_t launch_hex_wide_piece(const HexWideParams& w, uint32_t waves, int piece, hipStream_t s);
+
+// ---- Alternation strings (yr_amd_scanner_set_alternations; alternations.hip) ----
+// A string whose programs are loop-free yr_re_exec programs (hex strings with
+// alternatives, regexps without * and +) is measured one WAVE per record from
+// a table of fixed-size instructions the host decodes at upload: instruction
+// i of a program in lane i, its position set (bit b: bytes_matched = b) in
+// lane i of a VGPR pair, every byte test one vector compare whose result is
+// the wave mask.
+constexpr uint32_t kAltMaxInsns = 64;     // a program's instructions live in the wave's lanes
+constexpr uint32_t kAltClassWords = 9;    // RE_CLASS: 8 words of bitmap, then `negated`
+enum AltOp : uint8_t {
+  kAltByte = 0,    // ((c & b) == a) != flag     LITERAL / NOT_ / MASKED_ / MASKED_NOT_
+  kAltAny,         // DOT_ALL || c != 0x0A
+  kAltClass,       // bit c of class a | b << 16, != its negated byte
+  kAltWord,        // \w, flag: \W
+  kAltSpace,       // \s, flag: \S
+  kAltDigit,       // \d, flag: \D
+  kAltRepeat,      // REPEAT_ANY {a, b}; flag: greedy
+  kAltSplit,       // flag 0: SPLIT_A (prefers next), 1: SPLIT_B (prefers target)
+  kAltJump,
+  kAltMatch,
+};
+struct AltInsn {
+  uint8_t op, next, target, flag;   // next / target: instruction INDICES, above its own
+  uint16_t a, b;
+};
+static_assert(sizeof(AltInsn) == 8, "decoded instruction layout");
+// Per pool entry: its programs in the instruction table (n_fwd 0: not an
+// alternation string's entry; n_bwd 0: no backward program).
+struct AltProg {
+  uint32_t fwd, bwd;
+  uint8_t n_fwd, n_bwd;
+  uint16_t pad;
+};
+struct AltTables {
+  const AltProg* progs;         // [n_pool]
+  const AltInsn* insns;
+  const uint32_t* classes;      // [..][kAltClassWords]
+  const uint8_t* str_alt;       // [n_strings] 1: an alternation string
+};
+// A struct of its own: HexWideParams is a kernel argument of the kernels
+// above, which stay what they are.  w.queue / w.qlen are the wide path's (its
+// queue stays empty with `wide` 0), w.icount / w.istart are used either way.
+struct AltParams {
+  HexWideParams w;
+  AltTables t;
+  uint32_t* queue;              // [qcap] the queued alternation records
+  uint32_t* qlen;
+  uint32_t qcap;
+  uint64_t* qlen_out;           // qlen for the host (pinned)
+  uint32_t wide;                // the wave-wide path of the hex class is on too
+};
+// The measure pass with both queues: the wide path's clear, the twin of
+// hex_measure_queue_kernel that queues alternation records too, one wave per
+// queued alternation record, (wide) one wave per queued wide record, the recount.
+hipError_t launch_alt_measure(const AltParams& a, uint32_t waves, hipStream_t s);
+
 // ---- Chained strings (yr_amd_scanner_set_chains; chains.hip) ----
 // libyara splits a hex string at every jump wider than
 // YR_STRING_CHAINING_THRESHOLD into a chain S0 <- S1 <- ... (chained_to links

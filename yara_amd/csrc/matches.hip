@@ -1147,6 +1147,19 @@ hipError_t launch_hex_wide_measure(const HexWideParams& w, uint32_t waves, hipSt
   return hipGetLastError();
 }
 
+hipError_t launch_hex_wide_piece(const HexWideParams& w, uint32_t waves, int piece, hipStream_t s) {
+  const uint64_t n = w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || w.qcap == 0 || piece < 0 || piece > 2) return hipErrorInvalidValue;
+  if (piece == 0)
+    hipLaunchKernelGGL(hex_wide_clear_kernel, dim3(1), dim3(1), 0, s, w);
+  else if (piece == 1)
+    hipLaunchKernelGGL(hex_wide_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, w);
+  else
+    hipLaunchKernelGGL(hex_wide_recount_kernel, match_grid(n), dim3(256), 0, s, w);
+  return hipGetLastError();
+}
+
 hipError_t launch_hex_wide_expand(const HexWideParams& w, uint32_t waves, hipStream_t s) {
   const HexMatchParams& p = w.h;
   if (p.m.n == 0 || p.n_items == 0) return hipSuccess;

@@ -128,6 +128,15 @@ struct yr_amd_tables {
   std::vector<uint8_t> h_chain_settled;
   uint32_t* d_chain_words = nullptr;
   ChainTables d_chain{};
+
+  // alternation strings (yr_amd_tables_alternation_strings; matches.h AltTables):
+  // decided and decoded when the programs are attached -- the host copy of the
+  // class, and on device tables one allocation that d_alt points into
+  bool has_programs = false;
+  std::vector<uint8_t> h_alt_string;
+  uint32_t n_alt_strings = 0;
+  uint32_t* d_alt_words = nullptr;
+  AltTables d_alt{};
 };
 
 struct yr_amd_scanner {
@@ -234,7 +243,7 @@ struct yr_amd_scanner {
   size_t mhist_cap = 0;
   uint64_t* d_mhchunk = nullptr;
   size_t mhchunk_cap = 0;
-  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued, chain items}
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued, chain items, alternation records queued}
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
@@ -280,6 +289,11 @@ struct yr_amd_scanner {
   // chained strings (yr_amd_scanner_set_chains; matches.h ChainParams): one
   // workspace, laid out per call by match_device_hex
   bool chains = false;
+  // alternation strings (yr_amd_scanner_set_alternations; matches.h AltParams):
+  // [1 + cap]: the queue's length, the queued records
+  bool alternations = false;
+  uint32_t* d_aqueue = nullptr;
+  size_t aqueue_cap = 0;
   uint64_t* d_chain_ws = nullptr;
   size_t chain_ws_cap = 0;
   // the batch's own setting (yr_amd_scanner_set_batch_chains; matches.h
@@ -485,7 +499,7 @@ int yr_amd_tables_destroy(yr_amd_tables* t) {
   if (t == nullptr) return YR_AMD_SUCCESS;
   for (void* p : {(void*)t->d_filter, (void*)t->d_exact, (void*)t->d_nodes, (void*)t->d_kc, (void*)t->d_pool,
                   (void*)t->d_str_bytes, (void*)t->d_lowercase, (void*)t->d_re_code,
-                  (void*)t->d_pool_string, (void*)t->d_chain_words})
+                  (void*)t->d_pool_string, (void*)t->d_chain_words, (void*)t->d_alt_words})
     if (p) (void)hipFree(p);
   delete t;
   return YR_AMD_SUCCESS;
@@ -583,7 +597,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff, (void*)s->d_hkeys,
                   (void*)s->d_hmeas, (void*)s->d_hsets, (void*)s->d_hrest, (void*)s->d_hblock,
                   (void*)s->d_hchunk, (void*)s->d_wqueue, (void*)s->d_wsets, (void*)s->d_wcount,
-                  (void*)s->d_chain_ws})
+                  (void*)s->d_chain_ws, (void*)s->d_aqueue})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1449,6 +1463,236 @@ void key_classes(yr_amd_tables* t) {
 }  // namespace
 }  // extern "C++"
 
+extern "C++" {
+namespace {
+constexpr uint32_t kAltExcluded = kStrLiteral | kStrFastRegexp | kStrChainPart | kStrChainTail |
+                                  kStrWide | kStrNoCase | kStrFullWord | kStrXor | kStrBase64Any;
+constexpr uint64_t kAltFiberLimit = 1024;   // RE_MAX_FIBERS (limits.h)
+
+// One program of an alternation string (include/yara_amd.h
+// yr_amd_tables_alternation_strings, condition 2 and 3): loop-free -- every
+// instruction reachable from the entry is a byte test, REPEAT_ANY, SPLIT, JUMP
+// or MATCH, every SPLIT / JUMP target lies above the instruction, at most
+// kAltMaxInsns instructions, no split id used twice -- and an upper bound on
+// the fibers yr_re_exec can hold below RE_MAX_FIBERS.  The
+// decoded instructions (matches.h AltInsn, indices in address order) are
+// appended to insns, its classes to classes.
+bool alt_program(const uint8_t* c, uint32_t len, std::vector<AltInsn>& insns,
+                 std::vector<uint32_t>& classes, uint64_t* bound_out) {
+  if (bound_out) *bound_out = 0;
+  if (len == 0) return false;
+  std::vector<uint8_t> seen(len, 0);
+  std::vector<uint32_t> work{0};
+  while (!work.empty()) {
+    uint32_t ip = work.back();
+    work.pop_back();
+    while (true) {
+      if (ip >= len) return false;
+      if (seen[ip]) break;
+      seen[ip] = 1;
+      const uint8_t op = c[ip];
+      const uint32_t sz = re_op_size(op);
+      if (sz == 0 || ip + sz > len) return false;
+      if (op == kOpMatch) break;
+      if (op == kOpJump || op == kOpSplitA || op == kOpSplitB) {
+        const int32_t d = re_i16(c + ip + (op == kOpJump ? 1 : 2));
+        if (d <= 0) return false;   // a backward edge (or a jump to itself)
+        if (op == kOpJump) {
+          ip += (uint32_t)d;
+          continue;
+        }
+        work.push_back(ip + (uint32_t)d);
+      } else if (op == kOpRepeatAnyGreedy || op == kOpRepeatAnyUngreedy) {
+        if (re_u16(c + ip + 1) > re_u16(c + ip + 3)) return false;
+      } else if (!(op == kOpAny || op == kOpLiteral || op == kOpNotLiteral || op == kOpMaskedLiteral ||
+                   op == kOpMaskedNotLiteral || op == kOpClass || op == kOpWordChar ||
+                   op == kOpNonWordChar || op == kOpSpace || op == kOpNonSpace || op == kOpDigit ||
+                   op == kOpNonDigit)) {
+        return false;   // REPEAT_START / _END, \b \B ^ $
+      }
+      ip += sz;
+    }
+  }
+  std::vector<uint32_t> addr;
+  std::vector<int32_t> index(len, -1);
+  for (uint32_t ip = 0; ip < len; ++ip)
+    if (seen[ip]) {
+      index[ip] = (int32_t)addr.size();
+      addr.push_back(ip);
+    }
+  const uint32_t n = (uint32_t)addr.size();
+  if (n > kAltMaxInsns) return false;
+  bool split_id[256] = {};
+  const size_t first = insns.size(), first_class = classes.size();
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t ip = addr[i];
+    const uint8_t op = c[ip];
+    AltInsn in{};
+    const uint32_t after = ip + re_op_size(op);
+    in.next = (op == kOpMatch || op == kOpJump) ? 0 : (uint8_t)index[after];
+    switch (op) {
+      case kOpAny: in.op = kAltAny; break;
+      case kOpLiteral: case kOpNotLiteral:
+        in.op = kAltByte; in.a = c[ip + 1]; in.b = 0xFF; in.flag = op == kOpNotLiteral; break;
+      case kOpMaskedLiteral: case kOpMaskedNotLiteral:
+        in.op = kAltByte; in.a = c[ip + 1]; in.b = c[ip + 2]; in.flag = op == kOpMaskedNotLiteral; break;
+      case kOpClass: {
+        const uint32_t k = (uint32_t)(classes.size() / kAltClassWords);
+        in.op = kAltClass; in.a = (uint16_t)k; in.b = (uint16_t)(k >> 16);
+        for (uint32_t w = 0; w < 8; ++w) classes.push_back((uint32_t)re_i32(c + ip + 2 + 4 * w));
+        classes.push_back(c[ip + 1]);   // RE_CLASS.negated
+        break;
+      }
+      case kOpWordChar: case kOpNonWordChar: in.op = kAltWord; in.flag = op == kOpNonWordChar; break;
+      case kOpSpace: case kOpNonSpace: in.op = kAltSpace; in.flag = op == kOpNonSpace; break;
+      case kOpDigit: case kOpNonDigit: in.op = kAltDigit; in.flag = op == kOpNonDigit; break;
+      case kOpRepeatAnyGreedy: case kOpRepeatAnyUngreedy:
+        in.op = kAltRepeat; in.a = re_u16(c + ip + 1); in.b = re_u16(c + ip + 3);
+        in.flag = op == kOpRepeatAnyGreedy; break;
+      case kOpSplitA: case kOpSplitB:
+        // (the reference kills a fiber that meets a split id twice in one sync, re.c:1482-1495:
+        // harmless only where an id names one instruction)
+        if (split_id[c[ip + 1]]) { insns.resize(first); classes.resize(first_class); return false; }
+        split_id[c[ip + 1]] = true;
+        in.op = kAltSplit; in.flag = op == kOpSplitB; in.target = (uint8_t)index[ip + re_i16(c + ip + 2)];
+        break;
+      case kOpJump: in.op = kAltJump; in.target = (uint8_t)index[ip + re_i16(c + ip + 1)]; break;
+      default: in.op = kAltMatch; break;
+    }
+    insns.push_back(in);
+  }
+  // arrive[i]: the fibers one fiber arriving at instruction i becomes in
+  // _yr_re_fiber_sync, with multiplicity; the bound: the entry's, plus per
+  // resting state (instruction, rc) what its fiber becomes after its byte
+  auto sat = [](uint64_t x) { return std::min<uint64_t>(x, 1u << 20); };
+  std::vector<uint64_t> arrive(n, 1);
+  uint64_t bound = 0;
+  for (uint32_t i = n; i-- > 0;) {
+    const AltInsn& in = insns[first + i];
+    if (in.op == kAltJump) arrive[i] = arrive[in.target];
+    else if (in.op == kAltSplit) arrive[i] = sat(arrive[in.next] + arrive[in.target]);
+    else if (in.op == kAltRepeat) arrive[i] = in.a == 0 ? sat(1 + arrive[in.next]) : 1;
+    if (in.op == kAltMatch) bound += 1;
+    else if (in.op == kAltRepeat) bound += ((uint64_t)in.b + 1) * (1 + arrive[in.next]);
+    else if (in.op <= kAltDigit) bound += arrive[in.next];
+    bound = std::min<uint64_t>(bound, 1ull << 40);
+  }
+  bound += arrive[0];
+  if (bound_out) *bound_out = bound;
+  if (bound >= kAltFiberLimit) {
+    insns.resize(first);
+    classes.resize(first_class);
+    return false;
+  }
+  return true;
+}
+
+// The class and the device tables, once flags, pool strings and programs are known.
+int attach_alternations(yr_amd_tables* t, const std::vector<uint32_t>& pool_string,
+                        const std::vector<DevRe>& re, const uint8_t* code) {
+  const uint32_t n_strings = (uint32_t)t->h_str_flags.size(), n_pool = (uint32_t)re.size();
+  std::vector<uint8_t> alt(n_strings, 0), entries(n_strings, 0);
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    const uint32_t f = t->h_str_flags[k];
+    alt[k] = (f & kStrAscii) && !(f & kAltExcluded) ? 1 : 0;
+  }
+  std::vector<AltProg> progs(n_pool, AltProg{0, 0, 0, 0, 0});
+  std::vector<AltInsn> insns;
+  std::vector<uint32_t> classes;
+  for (uint32_t k = 0; k < n_pool; ++k) {
+    const uint32_t s = pool_string[k];
+    if (!alt[s]) continue;
+    entries[s] = 1;
+    AltProg& p = progs[k];
+    p.fwd = (uint32_t)insns.size();
+    bool ok = re[k].fwd_len > 0 && alt_program(code + re[k].fwd_off, re[k].fwd_len, insns, classes, nullptr);
+    if (ok) p.n_fwd = (uint8_t)(insns.size() - p.fwd);
+    p.bwd = (uint32_t)insns.size();
+    if (ok && re[k].bwd_len > 0) {
+      ok = alt_program(code + re[k].bwd_off, re[k].bwd_len, insns, classes, nullptr);
+      if (ok) p.n_bwd = (uint8_t)(insns.size() - p.bwd);
+    }
+    if (!ok) alt[s] = 0;
+  }
+  t->n_alt_strings = 0;
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    if (!entries[k]) alt[k] = 0;   // (no pool entry: no record could ever name it)
+    t->n_alt_strings += alt[k];
+  }
+  for (uint32_t k = 0; k < n_pool; ++k)
+    if (!alt[pool_string[k]]) progs[k].n_fwd = progs[k].n_bwd = 0;
+  t->h_alt_string = alt;
+  t->has_programs = true;
+  if (t->device < 0) return YR_AMD_SUCCESS;
+  // one allocation: progs (3 words each), insns (2 each), classes, str_alt
+  static_assert(sizeof(AltProg) == 12 && sizeof(AltInsn) == 8, "table layout");
+  const size_t at_insns = 3 * (size_t)n_pool + ((3 * (size_t)n_pool) & 1);   // (8-byte aligned)
+  std::vector<uint32_t> w(at_insns + 2 * insns.size() + classes.size() + (n_strings + 3) / 4 + 1, 0);
+  if (n_pool > 0) memcpy(w.data(), progs.data(), 12 * (size_t)n_pool);
+  if (!insns.empty()) memcpy(w.data() + at_insns, insns.data(), 8 * insns.size());
+  const size_t at_classes = at_insns + 2 * insns.size();
+  if (!classes.empty()) memcpy(w.data() + at_classes, classes.data(), 4 * classes.size());
+  const size_t at_str = at_classes + classes.size();
+  if (n_strings > 0) memcpy(w.data() + at_str, alt.data(), n_strings);
+  int r = upload(t->d_alt_words, w.data(), w.size());
+  if (r) {
+    if (t->d_alt_words) (void)hipFree(t->d_alt_words);
+    t->d_alt_words = nullptr;
+    return r;
+  }
+  const uint32_t* d = t->d_alt_words;
+  t->d_alt.progs = reinterpret_cast<const AltProg*>(d);
+  t->d_alt.insns = reinterpret_cast<const AltInsn*>(d + at_insns);
+  t->d_alt.classes = d + at_classes;
+  t->d_alt.str_alt = reinterpret_cast<const uint8_t*>(d + at_str);
+  return YR_AMD_SUCCESS;
+}
+}  // namespace
+}  // extern "C++"
+
+// Not declared in include/yara_amd.h: alt_program on one program, for the CPU
+// tests (tests/test_alternation_abi.py): 1 if it is loop-free with a fiber
+// bound below RE_MAX_FIBERS, else 0; *bound = the bound (0: not loop-free).
+int yr_amd__alternation_program(const uint8_t* code, uint32_t len, uint64_t* bound) {
+  if (code == nullptr) return -1;
+  std::vector<AltInsn> insns;
+  std::vector<uint32_t> classes;
+  return alt_program(code, len, insns, classes, bound) ? 1 : 0;
+}
+
+// Not declared in include/yara_amd.h: the programs of HOST-ONLY tables (device
+// < 0, flags attached), all that yr_amd_tables_alternation_strings reads of
+// them.  yr_amd_tables_load_yarc calls it for such tables.
+int yr_amd__tables_set_host_programs(yr_amd_tables* t, const uint32_t* pool_string, uint32_t n_pool,
+                                     const uint32_t* fwd_off, const uint32_t* fwd_len,
+                                     const uint32_t* bwd_off, const uint32_t* bwd_len,
+                                     const uint8_t* code, uint64_t code_len) {
+  if (t == nullptr || t->device >= 0 || !t->has_str_flags || t->has_programs)
+    return YR_AMD_INVALID_ARGUMENT;
+  if (n_pool != t->flat.pool_next.size()) return YR_AMD_INVALID_ARGUMENT;
+  if (n_pool > 0 && (pool_string == nullptr || fwd_off == nullptr || fwd_len == nullptr ||
+                     bwd_off == nullptr || bwd_len == nullptr))
+    return YR_AMD_INVALID_ARGUMENT;
+  if (code_len > 0 && code == nullptr) return YR_AMD_INVALID_ARGUMENT;
+  std::vector<DevRe> re(n_pool);
+  for (uint32_t k = 0; k < n_pool; ++k) {
+    if (pool_string[k] >= t->h_str_flags.size()) return YR_AMD_INVALID_ARGUMENT;
+    re[k] = fwd_len[k] == 0 ? DevRe{0, 0, 0, 0} : DevRe{fwd_off[k], fwd_len[k], bwd_off[k], bwd_len[k]};
+    if ((uint64_t)re[k].fwd_off + re[k].fwd_len > code_len ||
+        (uint64_t)re[k].bwd_off + re[k].bwd_len > code_len)
+      return YR_AMD_INVALID_ARGUMENT;
+  }
+  return attach_alternations(t, std::vector<uint32_t>(pool_string, pool_string + n_pool), re, code);
+}
+
+int yr_amd_tables_alternation_strings(const yr_amd_tables* t, uint8_t* out, uint32_t n_strings) {
+  if (t == nullptr || !(t->has_strings || t->has_str_flags) || n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && out == nullptr) || !t->has_programs)
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_strings; ++k) out[k] = t->h_alt_string[k];
+  return YR_AMD_SUCCESS;
+}
+
 // Not declared in include/yara_amd.h: re_fiber_safe on one yr_re_exec
 // program, for the CPU tests (tests/test_guards.py): 1 if its run provably
 // stays below RE_MAX_FIBERS, else 0.
@@ -1544,7 +1788,7 @@ int yr_amd_tables_set_re_code(yr_amd_tables* t, uint32_t n_pool, const uint32_t*
                               hipMemcpyHostToDevice) != hipSuccess)
     return YR_AMD_INTERNAL_FATAL_ERROR;
   key_classes(t);
-  return YR_AMD_SUCCESS;
+  return attach_alternations(t, t->h_pool_string, re, code);
 }
 
 int yr_amd_verify_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_verify_rec** d_records,
@@ -1763,7 +2007,7 @@ int reallocate(T*& p, size_t need) {
 // two CSR offset arrays too.
 int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
   if (s->h_msum == nullptr) {
-    if (hipHostMalloc((void**)&s->h_msum, 6 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
+    if (hipHostMalloc((void**)&s->h_msum, 8 * sizeof(uint64_t), hipHostMallocCoherent) != hipSuccess) {
       s->h_msum = nullptr;
       return YR_AMD_INSUFFICIENT_MEMORY;
     }
@@ -1801,8 +2045,10 @@ int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
 // chains: the records of settled chains become events and these the heads'
 // items (matches.h ChainParams), all of it queued ahead of the first wait --
 // the same two waits.
+// alts: the records of alternation strings are queued and measured one wave
+// each (matches.h AltParams), beside the wide path's queue when that is on.
 int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n, uint64_t* nm,
-                     uint64_t* nr, bool chains) {
+                     uint64_t* nr, bool chains, bool alts) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
   // (the pinned totals; the items' arrays grow below.  With chains the events'
@@ -1876,12 +2122,15 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   // a larger queue: the capacity follows the wide records, not the records.
   const bool wide = s->hex_wide;
   const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
-  uint64_t queued = 0;
-  for (size_t qcap = std::max<size_t>(s->wqueue_cap, 257) - 1;; qcap = std::max<size_t>(queued, 2 * qcap)) {
-    if (wide) {
+  AltParams a{};
+  uint64_t queued = 0, alt_queued = 0;
+  size_t aqcap = std::max<size_t>(s->aqueue_cap, 257) - 1;
+  for (size_t qcap = std::max<size_t>(s->wqueue_cap, 257) - 1;;) {
+    if (wide || alts) {   // (alts alone: the wide queue stays empty, the per-record counts are used)
       r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + qcap);
-      if (!r) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
+      if (!r && wide) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
       if (!r) r = grow_geo(s->d_wcount, s->wcount_cap, 2 * n);
+      if (!r && alts) r = grow_geo(s->d_aqueue, s->aqueue_cap, 1 + aqcap);
       if (r) return r;
       w.h = p;
       w.qlen = s->d_wqueue;
@@ -1892,8 +2141,19 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
       w.icount = s->d_wcount;
       w.istart = s->d_wcount + n;
     }
+    if (alts) {
+      a.w = w;
+      a.t = t->d_alt;
+      a.qlen = s->d_aqueue;
+      a.queue = s->d_aqueue + 1;
+      a.qcap = (uint32_t)std::min<size_t>(s->aqueue_cap - 1, kMatchMaxRecords);
+      a.qlen_out = s->d_mhsum + 6;
+      a.wide = wide ? 1u : 0u;
+    }
     // measure -> the offsets of the rest and of the items -> the rest; wait
-    if (wide)
+    if (alts)
+      HIP_TRY(launch_alt_measure(a, wide_waves, s->stream));
+    else if (wide)
       HIP_TRY(launch_hex_wide_measure(w, wide_waves, s->stream));
     else
       HIP_TRY(launch_hex_measure(p, s->stream));
@@ -1922,8 +2182,13 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     queued = wide ? s->h_msum[4] : 0;
-    if (queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
-    if (!wide || queued <= w.qcap) break;
+    alt_queued = alts ? s->h_msum[6] : 0;
+    if (queued > n || alt_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    // a queue that overflowed grows to what was appended, and the pass runs again
+    const bool wide_over = wide && queued > w.qcap, alt_over = alts && alt_queued > a.qcap;
+    if (!wide_over && !alt_over) break;
+    if (wide_over) qcap = std::max<size_t>(queued, 2 * qcap);
+    if (alt_over) aqcap = std::max<size_t>(alt_queued, 2 * aqcap);
   }
   *nr = s->h_msum[0];
   const uint64_t hex_items = s->h_msum[3];
@@ -1936,6 +2201,9 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   if (debug_level() >= 1 && wide)
     fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_device()\n",
             (unsigned long long)n, (unsigned long long)queued);
+  if (debug_level() >= 1 && alts)
+    fprintf(stderr, "- %llu verify calls, %llu queued as alternation records // yr_amd_match_device()\n",
+            (unsigned long long)n, (unsigned long long)alt_queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   *nm = 0;
   if (items == 0) return YR_AMD_SUCCESS;
@@ -1954,7 +2222,7 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort; distinct keys -> their offsets -> the matches; wait
-  if (wide) {
+  if (wide || alts) {
     w.h = p;
     HIP_TRY(launch_hex_wide_expand(w, wide_waves, s->stream));
   } else {
@@ -2115,6 +2383,12 @@ int yr_amd_scanner_set_chains(yr_amd_scanner* s, int enable) {
   return YR_AMD_SUCCESS;
 }
 
+int yr_amd_scanner_set_alternations(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->alternations = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_match_rec** d_matches,
                         uint64_t* n_matches, const yr_amd_verify_rec** d_rest, uint64_t* n_rest) {
   if (s == nullptr || s->pending || !s->scanned || s->batch || !s->tables->has_strings)
@@ -2141,8 +2415,10 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
   if (r) return r;
   if (n > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   uint64_t nm = 0, nr = 0;
+  // alternation strings (yr_amd_scanner_set_alternations): with the hex class only
+  const bool alts = hex && s->alternations && t->n_alt_strings > 0;
   if (n > 0 && (hex || chains)) {   // (the events are assembled behind the records' measure pass)
-    r = match_device_hex(s, d_rec, n, &nm, &nr, chains);
+    r = match_device_hex(s, d_rec, n, &nm, &nr, chains, alts);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n);

@@ -32,6 +32,13 @@
 #include "../../include/yara_amd.h"
 #include "re_program.h"
 
+// (scanner.cpp; not part of include/yara_amd.h)
+extern "C" int yr_amd__tables_set_host_programs(yr_amd_tables* t, const uint32_t* pool_string,
+                                                uint32_t n_pool, const uint32_t* fwd_off,
+                                                const uint32_t* fwd_len, const uint32_t* bwd_off,
+                                                const uint32_t* bwd_len, const uint8_t* code,
+                                                uint64_t code_len);
+
 namespace {
 
 constexpr uint32_t kArenaVersion = 19;
@@ -255,6 +262,10 @@ extern "C" int yr_amd_tables_load_yarc(const uint8_t* file, size_t file_size, in
     std::vector<uint32_t> flags(n_strings);
     for (uint32_t k = 0; k < n_strings; ++k) flags[k] = st[k].flags;
     r = yr_amd_tables_set_string_flags(t, flags.data(), n_strings);
+    // ... and the programs, for yr_amd_tables_alternation_strings
+    if (!r)
+      r = yr_amd__tables_set_host_programs(t, ps.data(), n_pool, fo.data(), fl.data(), bo.data(),
+                                           bl.data(), code.data(), code.size());
     if (r) {
       yr_amd_tables_destroy(t);
       return r;
