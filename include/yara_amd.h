@@ -741,7 +741,8 @@ int yr_amd_scanner_set_chains(yr_amd_scanner* scanner, int enable); /* 0 default
  * outside the window.  A chain with an alternation part stays unsettled.
  * Read by yr_amd_match_device and yr_amd_scan_block_matches only, and only
  * when the scanner's classes include YR_AMD_MATCH_HEX; the batch calls never
- * read it.  With the setting on and tables without programs the two calls
+ * read it (theirs is yr_amd_scanner_set_batch_alternations below).  With the
+ * setting on and tables without programs the two calls
  * return YR_AMD_INVALID_ARGUMENT (as they do for the hex class); with it off
  * they launch what they launched before.  Should the records outgrow the
  * device queue, the first wait sees it, the queue grows and the measure pass
@@ -1084,6 +1085,44 @@ int yr_amd_scanner_set_batch_hex_wide(yr_amd_scanner* scanner, int enable);
  */
 int yr_amd_scanner_set_batch_chains(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
 int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* scanner, uint32_t* waves);
+
+/*
+ * The batch's alternation strings.  0 (default): every record of an
+ * alternation string of a batch stays in the rest, and the batch stage
+ * launches exactly what it launches without this setting.  1:
+ * yr_amd_match_batch_device and yr_amd_scan_batch_matches (and through them
+ * gathered batches) also settle the records of the strings
+ * yr_amd_tables_alternation_strings names, per buffer, as
+ * yr_amd_scanner_set_alternations does for a single block.  Read only by the
+ * batch match calls, and only when the BATCH classes include
+ * YR_AMD_MATCH_HEX; the single-block calls never read it, and the batch calls
+ * still never read yr_amd_scanner_set_alternations.
+ *
+ * With the setting on, buffer k of a batch gets exactly the matches and the
+ * rest that yr_amd_scan_block_matches(data_k, size_k, bases[k]) returns for
+ * that buffer alone on a scanner with yr_amd_scanner_set_alternations(1) and
+ * the same classes, wide setting and chains setting:
+ *   - the buffer is the whole block of both runs: max_bytes_matched is
+ *     min(size_k - local offset, YR_RE_SCAN_LIMIT) forwards and min(local
+ *     offset, YR_RE_SCAN_LIMIT) backwards, and no byte of a gap or of a
+ *     neighbouring buffer is read -- a batch buffer is never a window;
+ *   - F is the bytes_matched of the highest-priority path to MATCH, every
+ *     backward bytes_matched B a match {local offset - B, B + F}, xor_key 0;
+ *     one entry per (buffer, string, local offset), the first record in
+ *     record order supplying length and pool_index; match_off[] and
+ *     rest_off[] count them;
+ *   - a record stays in the rest, in place, when no path reaches MATCH, when a
+ *     run would have to read input byte 64 or later, or when the backward
+ *     result is exactly 64;
+ *   - a chain with an alternation part stays unsettled.
+ * With the setting on and tables without programs the batch match calls return
+ * YR_AMD_INVALID_ARGUMENT (as they do for the hex class),
+ * yr_amd_scan_batch_matches before any copy.  The stage still waits twice;
+ * should the records outgrow the device queue, the first wait sees it, the
+ * queue grows and the measure pass runs again (one loop with the wide path's
+ * queue).  NULL scanner or a value other than 0/1: YR_AMD_INVALID_ARGUMENT.
+ */
+int yr_amd_scanner_set_batch_alternations(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
 
 /*
  * ---- Block pipeline ----

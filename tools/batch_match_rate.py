@@ -46,6 +46,18 @@ alternating in one process, medians of --reps after a warm-up with min..max:
   - what a caller had for the second input before: one yr_amd_scan_block_matches
     with yr_amd_scanner_set_hex_wide(1) per buffer on the first --sample
     buffers, wall clock, EXTRAPOLATED by n / sample.
+
+    python tools/batch_match_rate.py --alternations [--reps 10] [--parent-tree DIR --rounds 5]
+                                     [--out profiles/batch_alternation_match_rates.json]
+
+The batch's alternation strings (yr_amd_scanner_set_batch_alternations), classes
+LITERAL | HEX, 256 MiB of rx's planted input (as tools/match_rate.py
+--alternations) cut into the same two workloads: the setting off and on
+alternating in one process, medians with min..max, matches and rest for both.
+With --parent-tree the setting is left off and the same calls are timed on this
+tree's library and on another build's (the parent commit's), one child process
+each, alternating --rounds times: the idle cost of the change next to the
+run-to-run spread the same runs show.
 """
 import argparse
 import ctypes
@@ -56,7 +68,8 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+# (YARA_AMD_PACKAGE_ROOT: another build's yara_amd package with its library, --parent-tree's child)
+sys.path.insert(0, os.environ.get("YARA_AMD_PACKAGE_ROOT") or REPO)
 
 WORKLOADS = [(65536, 4 << 10), (4096, 64 << 10)]
 
@@ -268,6 +281,110 @@ def hex_wide_leg(a):
             f.write("\n")
 
 
+def alternations_leg(a):
+    import subprocess
+    med = lambda v: round(statistics.median(v), 4)   # noqa: E731
+    span = lambda v: [round(min(v), 4), round(max(v), 4)]   # noqa: E731
+    total = (256 << 20) // a.scale
+    if a.parent_tree and not a.child:
+        out = {"bytes": total, "reps": a.reps, "rounds": a.rounds, "runs": []}
+        sides = {"this": None, "parent": os.path.abspath(a.parent_tree)}
+        meds = {}
+        for _ in range(a.rounds):
+            for side, lib in sides.items():
+                env = dict(os.environ)
+                if lib:
+                    env["YARA_AMD_PACKAGE_ROOT"] = lib
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--alternations", "--child",
+                                    "--reps", str(a.reps), "--scale", str(a.scale), "--buffers",
+                                    str(a.buffers)], env=env, capture_output=True, text=True, timeout=300)
+                if r.returncode != 0:   # (nothing more is started on the device)
+                    sys.exit("child (%s) failed with %d:\n%s" % (side, r.returncode, r.stderr[-2000:]))
+                ms = json.loads(r.stdout.strip().splitlines()[-1])["off_ms"]
+                out["runs"].append({"side": side, "off_ms": ms})
+                for k, v in ms.items():
+                    meds.setdefault(k, {s: [] for s in sides})[side].append(v)
+        out["idle"] = {k: {"this_median_ms": med(v["this"]), "this_min_max_ms": span(v["this"]),
+                           "parent_median_ms": med(v["parent"]), "parent_min_max_ms": span(v["parent"]),
+                           "this_over_parent": round(med(v["this"]) / med(v["parent"]), 4)}
+                       for k, v in meds.items()}
+        print(json.dumps(out["idle"]), flush=True)
+    else:
+        import numpy as np
+        import torch
+        import yara_amd
+        from yara_amd import _lib
+        sys.path[:0] = [os.path.join(REPO, "tests", "golden")]
+        sys.path.append(REPO)   # (oracle; behind a --parent-tree package root)
+        import oracle
+        import planted
+        L = _lib.lib()
+        stream = torch.cuda.Stream()
+        t = yara_amd.Tables.from_npz(os.path.join(REPO, "tests", "golden", "tables", "rx.npz"), strings=True)
+        host = planted.rx_buffer(oracle.xorshift, total, 19)   # (rx_1M's generator at this size)
+        buf = torch.empty(total + 16, dtype=torch.uint8, device="cuda")
+        buf[:total] = torch.from_numpy(host).cuda()
+        torch.cuda.synchronize()
+        out = {"bytes": total, "reps": a.reps, "classes": "LITERAL | HEX", "input": "rx planted", "runs": []}
+        child = {}
+        for n, size in WORKLOADS:
+            if a.buffers and n != a.buffers:
+                continue
+            n = total // size
+            sizes = np.full(n, size, np.uint64)
+            starts = np.arange(n, dtype=np.uint64) * np.uint64(size)
+            sc = yara_amd.Scanner(t, stream=stream.cuda_stream)
+            sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+            sc.scan_batch_device(buf.data_ptr(), total, starts, sizes)
+            sc.batch_result()
+            p1, p2 = ctypes.c_void_p(), ctypes.c_void_p()
+            o1, o2 = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+
+            def stage(on):   # (ms, matches, rest): the device call alone
+                if on is not None:
+                    sc.set_batch_alternations(on)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                _lib.check("yr_amd_match_batch_device", L.yr_amd_match_batch_device(
+                    sc._h, None, ctypes.byref(p1), ctypes.byref(o1), ctypes.byref(p2), ctypes.byref(o2)))
+                e1.record(stream)
+                e1.synchronize()
+                return e0.elapsed_time(e1), int(o1[n]), int(o2[n])
+
+            if a.child:   # the setting is never touched: the same calls on either library
+                for _ in range(3):
+                    stage(None)
+                child["%dx%d" % (n, size)] = med([stage(None)[0] for _ in range(a.reps)])
+                sc.close()
+                continue
+            for _ in range(2):   # warm-up: buffers and the queue grown, clocks up
+                stage(False)
+                stage(True)
+            ms, count = {False: [], True: []}, {}
+            for _ in range(a.reps):   # alternating
+                for on in (False, True):
+                    v, m, r = stage(on)
+                    ms[on].append(v)
+                    count[on] = (m, r)
+            run = {"buffers": n, "buffer_bytes": size, "records": int(sc.verify_batch_device()[1][-1]),
+                   "off": {"matches": count[False][0], "rest": count[False][1],
+                           "match_batch_ms": med(ms[False]), "min_max_ms": span(ms[False])},
+                   "on": {"matches": count[True][0], "rest": count[True][1],
+                          "match_batch_ms": med(ms[True]), "min_max_ms": span(ms[True])},
+                   "added_ms": round(med(ms[True]) - med(ms[False]), 4),
+                   "alternation_records": count[False][1] - count[True][1]}
+            out["runs"].append(run)
+            print(json.dumps(run), flush=True)
+            sc.close()
+        if a.child:
+            print(json.dumps({"off_ms": child}), flush=True)
+            return
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sets", default="C,short")
@@ -280,7 +397,17 @@ def main():
                     help="the batch's hex class on config C's planted input instead of the sets")
     ap.add_argument("--hex-wide", action="store_true",
                     help="the batch's wave-wide path, off against on (see above)")
+    ap.add_argument("--alternations", action="store_true",
+                    help="the batch's alternation strings, off against on, on rx's planted input")
+    ap.add_argument("--parent-tree", default=None,
+                    help="with --alternations: a directory holding another build's yara_amd package "
+                         "(the parent commit's, with its library) to time the setting off against, "
+                         "alternating child processes")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.alternations:
+        return alternations_leg(a)
     if a.hex_wide:
         return hex_wide_leg(a)
     if a.hex:

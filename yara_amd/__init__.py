@@ -331,6 +331,7 @@ class Scanner:
         self._batch_chains = False   # set_batch_chains
         self._chains = False   # set_chains
         self._alternations = False   # set_alternations
+        self._batch_alternations = False   # set_batch_alternations
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -427,7 +428,8 @@ class Scanner:
         """Settle alternation strings too (yr_amd_scanner_set_alternations):
         the strings ``Tables.alternation_strings`` names, with the forward
         length of yr_re_exec's highest-priority path.  Read only while the
-        classes include MATCH_HEX; the batch calls never read it."""
+        classes include MATCH_HEX; the batch calls never read it (theirs is
+        set_batch_alternations)."""
         _lib.check("yr_amd_scanner_set_alternations",
                    _lib.lib().yr_amd_scanner_set_alternations(self._h, int(enable)))
         self._alternations = bool(enable)
@@ -503,9 +505,22 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_batch_chain_waves(self._h, ctypes.byref(w)))
         return w.value
 
-    def _with_batch_hex(self, hex, call, wide=False, chains=False):
+    def set_batch_alternations(self, enable: bool):
+        """Settle alternation strings in the BATCH match stage too
+        (yr_amd_scanner_set_batch_alternations): per buffer, what
+        ``set_alternations`` gives for that buffer alone, the strings those of
+        ``Tables.alternation_strings``.  Read only by the batch calls and only
+        while the batch classes include MATCH_HEX; the single-block calls
+        never read it."""
+        _lib.check("yr_amd_scanner_set_batch_alternations",
+                   _lib.lib().yr_amd_scanner_set_batch_alternations(self._h, int(enable)))
+        self._batch_alternations = bool(enable)
+
+    def _with_batch_hex(self, hex, call, wide=False, chains=False, alternations=False):
         # _with_hex for the batch calls' settings
         was, was_wide = self._batch_classes, self._batch_hex_wide
+        if not alternations or self._batch_alternations:
+            alternations = False
         if not hex or (was & MATCH_HEX):
             hex = False
         if not wide or was_wide:
@@ -518,9 +533,13 @@ class Scanner:
             self.set_batch_hex_wide(True)
         if chains:
             self.set_batch_chains(True)
+        if alternations:
+            self.set_batch_alternations(True)
         try:
             return call()
         finally:
+            if alternations:
+                self.set_batch_alternations(False)
             if chains:
                 self.set_batch_chains(False)
             if wide:
@@ -726,7 +745,7 @@ class Scanner:
 
     # -- final matches of a batch ------------------------------------------------
     def match_batch_device(self, bases=None, hex: bool = False, wide: bool = False,
-                           chains: bool = False):
+                           chains: bool = False, alternations: bool = False):
         """(matches, match_off, rest, rest_off) of the last completed batch scan
         (yr_amd_match_batch_device), copied to the host: buffer k's
         ``matches[match_off[k]:match_off[k + 1]]`` and
@@ -739,8 +758,13 @@ class Scanner:
         (set_batch_hex_wide), as ``string_matches(hex=True, wide=True)`` does
         for the buffer alone: by itself it does nothing.  ``chains=True``
         settles the chained strings for this call (set_batch_chains), as
-        ``string_matches(chains=True)`` does for the buffer alone."""
-        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide, chains)
+        ``string_matches(chains=True)`` does for the buffer alone.
+        ``alternations=True`` settles the alternation strings for this call
+        (set_batch_alternations), as ``string_matches(hex=True,
+        alternations=True)`` does for the buffer alone; like ``wide`` it goes
+        with the hex class."""
+        return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide, chains,
+                                    alternations)
 
     def _match_batch_device(self, bases):
         from ._hip import memcpy
@@ -763,14 +787,14 @@ class Scanner:
         return matches, match_off, rest, rest_off
 
     def batch_string_matches(self, buffers, bases=None, hex: bool = False, wide: bool = False,
-                             chains: bool = False):
+                             chains: bool = False, alternations: bool = False):
         """(matches, match_off, rest, rest_off) of a list of host buffers
         (yr_amd_scan_batch_matches): buffer k's slices equal
         ``string_matches(buffers[k], bases[k], hex=hex, wide=wide,
-        chains=chains)``.  One scan, one pre-verification and one match stage
-        for all of them."""
+        chains=chains, alternations=alternations)``.  One scan, one
+        pre-verification and one match stage for all of them."""
         return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases), wide,
-                                    chains)
+                                    chains, alternations)
 
     def _batch_string_matches(self, buffers, bases):
         bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
@@ -798,7 +822,8 @@ class Scanner:
         return matches, match_off, rest, rest_off
 
     def batch_string_matches_device(self, buffers, bases=None, hex: bool = False,
-                                    wide: bool = False, chains: bool = False):
+                                    wide: bool = False, chains: bool = False,
+                                    alternations: bool = False):
         """batch_string_matches for buffers in device memory (see
         batch_candidates_device), through the gather call."""
         ptrs, sizes = _device_buffers(buffers)
@@ -806,7 +831,8 @@ class Scanner:
             raise ValueError("one base per buffer")
         self.scan_batch_gather_device(ptrs, sizes)
         self.batch_result()
-        return self.match_batch_device(bases, hex=hex, wide=wide, chains=chains)
+        return self.match_batch_device(bases, hex=hex, wide=wide, chains=chains,
+                                       alternations=alternations)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

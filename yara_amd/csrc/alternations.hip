@@ -29,6 +29,10 @@
 // preferred branch whose R has the bit.  Position 64 (a consuming instruction
 // that passes at byte 63) is carried as one bit per INSTRUCTION; a run that
 // would have to read byte 64 leaves the record in the rest.
+//
+// The batch calls (yr_amd_scanner_set_batch_alternations; matches.h
+// BatchAltParams) run the same machinery per buffer: the queue
+// holds (record, buffer) pairs and alt_record gets the buffer as its block.
 #include "internal.h"
 #include "matches.h"
 #include "match_measure.h"
@@ -333,23 +337,27 @@ __global__ void alt_clear_kernel(AltParams a) { *a.qlen = 0; }
 // queue kernel left of the record -- its key, F, its set {mask, base 0}, the
 // item count -- which is what the narrow hex path leaves; anything else
 // leaves the record in the rest.
-__device__ void alt_record(const AltParams& a, uint32_t r, uint32_t* cls) {
-  const HexMatchParams& q = a.w.h;
+// The block of both runs is [data, data + size) and `offset` the record's
+// position in it: the scanned block, or -- a batch -- the record's own buffer
+// and its local offset.  Lane b is loaded only where b < max_bytes_matched, so
+// no byte outside the block is read.
+__device__ void alt_record(const AltTables& t, const HexWideParams& w, uint32_t r, const uint8_t* data,
+                           uint64_t size, uint64_t offset, uint32_t* cls) {
+  const HexMatchParams& q = w.h;
   const MatchParams& p = q.m;
   const uint32_t lane = threadIdx.x & 63u;
   const VerifyRec rec = p.recs[r];
-  const AltProg prog = a.t.progs[rec.pool_index];
-  const uint64_t offset = rec.offset;
-  if (prog.n_fwd == 0 || prog.n_fwd > kAltMaxInsns || prog.n_bwd > kAltMaxInsns || offset >= p.size)
+  const AltProg prog = t.progs[rec.pool_index];
+  if (prog.n_fwd == 0 || prog.n_fwd > kAltMaxInsns || prog.n_bwd > kAltMaxInsns || offset >= size)
     return;   // (never: what the measure pass appended)
   const bool dot_all = (p.pool[rec.pool_index].flags & kStrDotAll) != 0;
-  const uint8_t* d = p.data + offset;
+  const uint8_t* d = data + offset;
   AltRun run;
   // forwards: lane b holds data[offset + b]
-  int maxb = (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit);
+  int maxb = (int)min<uint64_t>(size - offset, (uint64_t)kReScanLimit);
   bool valid = (int)lane < maxb;
   uint32_t c = valid ? d[lane] : 0u;
-  if (!alt_load(a.t, prog.fwd, prog.n_fwd, c, valid, dot_all, cls, maxb, run)) return;
+  if (!alt_load(t, prog.fwd, prog.n_fwd, c, valid, dot_all, cls, maxb, run)) return;
   uint64_t M, top;
   bool mtop;
   if (alt_sets(run, M, mtop, top) != kAltOk) return;
@@ -364,7 +372,7 @@ __device__ void alt_record(const AltParams& a, uint32_t r, uint32_t* cls) {
     maxb = (int)min<uint64_t>(offset, (uint64_t)kReScanLimit);
     valid = (int)lane < maxb;
     c = valid ? *(d - 1 - (int)lane) : 0u;
-    if (!alt_load(a.t, prog.bwd, prog.n_bwd, c, valid, dot_all, cls, maxb, run)) return;
+    if (!alt_load(t, prog.bwd, prog.n_bwd, c, valid, dot_all, cls, maxb, run)) return;
     if (alt_sets(run, B, mtop, top) != kAltOk) return;
     // (bytes_matched 64 is outside HexSet's base-0 mask.  Position 64 at any other
     // instruction died above, as the reference's fiber does: max_bytes_matched is 64)
@@ -374,7 +382,7 @@ __device__ void alt_record(const AltParams& a, uint32_t r, uint32_t* cls) {
     p.keys[r] = (uint64_t)p.pool_string[rec.pool_index] << 32 | (offset & 0xFFFFFFFFull);
     p.meas[r] = MatchMeasure{F, 0u};
     q.sets[r] = HexSet{B, 0u, 0u};
-    a.w.icount[r] = (uint32_t)__popcll(B);
+    w.icount[r] = (uint32_t)__popcll(B);
   }
 }
 
@@ -389,7 +397,118 @@ __global__ __launch_bounds__(256) void alt_measure_kernel(AltParams a) {
        slot += gridDim.x * 4) {
     const uint32_t r = __builtin_amdgcn_readfirstlane(a.queue[slot]);
     if (r >= a.w.h.m.n) continue;   // (never)
-    alt_record(a, r, classes[wave]);
+    const MatchParams& p = a.w.h.m;
+    alt_record(a.t, a.w, r, p.data, p.size, p.recs[r].offset, classes[wave]);
+  }
+}
+
+// ---- The batch's alternation strings (matches.h BatchAltParams) ----
+
+// batch_hex_measure_queue_kernel's twin (matches.hip) with the second queue, as
+// alt_measure_queue_kernel is hex_measure_queue_kernel's: the record's buffer is
+// searched in rec_off once, here; a record of an alternation string inside its
+// buffer is a rest record for now and is appended to the alternation queue as
+// the pair (record, buffer).  Every batch buffer is whole -- never a window --
+// so the single-block twin's window test has no counterpart.  WIDE: the wide
+// records are queued as batch_hex_measure_queue_kernel queues them; else a
+// final hex string's record is measured as batch_hex_measure_kernel measures it.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void batch_alt_measure_queue_kernel(BatchAltParams a) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const BatchHexWideParams& b = a.b;
+  const HexWideParams& w = b.w;
+  const MatchParams& p = w.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool wide = false, alt = false;
+  uint32_t lo = 0;
+  if (r < p.n) {
+    uint32_t hi = b.nbuf;   // rec_off[lo] <= r < rec_off[hi]  (rec_off[nbuf] == n)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (b.rec_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    HexMatchParams q = w.h;
+    q.m.data = p.data + b.starts[lo];
+    q.m.size = b.sizes[lo];
+    q.m.win_lo = 0;
+    q.m.win_hi = q.m.size;
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    if (a.t.str_alt[p.pool_string[rec.pool_index]] != 0) {
+      m.length = 0;
+      m.xor_key = 0;
+      is_match = false;
+      alt = rec.offset < q.m.size;
+    } else if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      const int v = measure_hex<WIDE>(q, e, rec.offset, buf, m, set);
+      is_match = v == kHexMatch;
+      wide = WIDE && v == kHexWide;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(q.m, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? p.pool_string[rec.pool_index] : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    w.h.sets[r] = set;
+    b.buf[r] = lo;
+    w.icount[r] = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  if (WIDE) {
+    const uint64_t qmask = __ballot(wide);
+    if (qmask != 0) {   // (wave-uniform)
+      uint32_t at = 0;
+      if ((threadIdx.x & 63u) == 0) at = atomicAdd(w.qlen, (uint32_t)__popcll(qmask));
+      at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(qmask);
+      if (wide && at < w.qcap) {
+        w.queue[at] = (uint32_t)r;
+        b.qbuf[at] = lo;
+      }
+    }
+  }
+  const uint64_t amask = __ballot(alt);
+  if (amask != 0) {   // (wave-uniform)
+    uint32_t at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(a.qlen, (uint32_t)__popcll(amask));
+    at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(amask);
+    if (alt && at < a.qcap) {
+      a.queue[at] = (uint32_t)r;
+      a.qbuf[at] = lo;
+    }
+  }
+  // (the per-wave counts are hex_wide_recount_kernel's: they include both queues' results)
+}
+
+__global__ void batch_alt_clear_kernel(BatchAltParams a) { *a.qlen = 0; }
+
+// alt_measure_kernel for a batch: one WAVE per queued pair, a fixed grid
+// striding over the queue.  Record and buffer come from the queue entry, the
+// buffer's bounds from starts / sizes through scalar registers (one value for
+// the wave).  alt_record sees the buffer as the whole block of both runs --
+// position 0 at arena + starts[k], max_bytes_matched = min(size_k - local
+// offset, YR_RE_SCAN_LIMIT) forwards and min(local offset, ...) backwards --
+// and loads lane b only below that bound: no byte of a gap or of a
+// neighbouring buffer.
+__global__ __launch_bounds__(256) void batch_alt_measure_kernel(BatchAltParams a) {
+  __shared__ uint32_t classes[4][16];
+  const HexWideParams& w = a.b.w;
+  const MatchParams& p = w.h.m;
+  const uint32_t wave = threadIdx.x >> 6;
+  const uint32_t len = *a.qlen;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *a.qlen_out = len;
+  const uint32_t n = min(len, a.qcap);
+  for (uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave); slot < n;
+       slot += gridDim.x * 4) {
+    const uint32_t r = __builtin_amdgcn_readfirstlane(a.queue[slot]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(a.qbuf[slot]);
+    if (r >= p.n || k >= a.b.nbuf) continue;   // (never: what the measure pass appended)
+    alt_record(a.t, w, r, p.data + a.b.starts[k], a.b.sizes[k], p.recs[r].offset, classes[wave]);
   }
 }
 
@@ -416,6 +535,30 @@ hipError_t launch_alt_measure(const AltParams& a, uint32_t waves, hipStream_t s)
     if (e != hipSuccess) return e;
   }
   return launch_hex_wide_piece(a.w, waves, 2, s);
+}
+
+hipError_t launch_batch_alt_measure(const BatchAltParams& a, uint32_t waves, hipStream_t s) {
+  const HexWideParams& w = a.b.w;
+  const uint64_t n = w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || a.qcap == 0 || w.qcap == 0 || a.b.nbuf == 0) return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  // (kernels, not memsets: the stage may be recorded into a graph)
+  hipError_t e = launch_hex_wide_piece(w, waves, 0, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(batch_alt_clear_kernel, dim3(1), dim3(1), 0, s, a);
+  if (a.wide)
+    hipLaunchKernelGGL(batch_alt_measure_queue_kernel<true>, grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(batch_alt_measure_queue_kernel<false>, grid, dim3(256), 0, s, a);
+  hipLaunchKernelGGL(batch_alt_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (a.wide) {
+    e = launch_batch_hex_wide_waves(a.b, waves, s);
+    if (e != hipSuccess) return e;
+  }
+  return launch_hex_wide_piece(w, waves, 2, s);
 }
 
 }  // namespace yamd

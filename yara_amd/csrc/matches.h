@@ -327,6 +327,36 @@ struct AltParams {
 // queued alternation record, (wide) one wave per queued wide record, the recount.
 hipError_t launch_alt_measure(const AltParams& a, uint32_t waves, hipStream_t s);
 
+// ---- The batch's alternation strings (yr_amd_scanner_set_batch_alternations) ----
+// BatchHexWideParams and AltParams at once.  A queue entry is a pair, as the
+// batch's wide queue's: the record in queue[slot], its buffer in qbuf[slot];
+// the wave takes the buffer's bounds [arena + starts[k], + sizes[k]) from
+// there and sees the buffer as the whole block of both runs.  A settled record
+// leaves what the narrow hex path leaves, so the items' CSR (icount / istart,
+// launch_batch_hex_wide_offsets), the expansion, the sort, the unique pass and
+// match_off run unchanged.
+// A struct of its own: BatchHexWideParams and AltParams are kernel arguments
+// of the kernels above, which stay what they are.  b.w.queue / b.w.qlen /
+// b.qbuf are the wide path's (its queue stays empty with `wide` 0), b.w.icount
+// / b.w.istart are used either way.
+struct BatchAltParams {
+  BatchHexWideParams b;
+  AltTables t;
+  uint32_t* queue;              // [qcap] the queued alternation records
+  uint32_t* qbuf;               // [qcap] by queue slot: the queued record's buffer
+  uint32_t* qlen;
+  uint32_t qcap;
+  uint64_t* qlen_out;           // qlen for the host (pinned)
+  uint32_t wide;                // the batch's wave-wide path is on too
+};
+// launch_alt_measure for a batch: both queues cleared, the twin of
+// batch_hex_measure_queue_kernel that queues alternation records too, one wave
+// per queued alternation pair, (wide) one wave per queued wide pair, the recount.
+hipError_t launch_batch_alt_measure(const BatchAltParams& a, uint32_t waves, hipStream_t s);
+// The middle piece of launch_batch_hex_wide_measure on its own, for that
+// launcher: one wave per queued wide pair.
+hipError_t launch_batch_hex_wide_waves(const BatchHexWideParams& p, uint32_t waves, hipStream_t s);
+
 // ---- Chained strings (yr_amd_scanner_set_chains; chains.hip) ----
 // libyara splits a hex string at every jump wider than
 // YR_STRING_CHAINING_THRESHOLD into a chain S0 <- S1 <- ... (chained_to links

@@ -1182,6 +1182,14 @@ hipError_t launch_batch_hex_wide_measure(const BatchHexWideParams& p, uint32_t w
   return hipGetLastError();
 }
 
+hipError_t launch_batch_hex_wide_waves(const BatchHexWideParams& p, uint32_t waves, hipStream_t s) {
+  const uint64_t n = p.w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || p.w.qcap == 0 || p.nbuf == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_hex_wide_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
 hipError_t launch_batch_hex_wide_offsets(const BatchHexWideParams& p, hipStream_t s) {
   const uint64_t n = p.w.h.m.n;
   if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;

@@ -289,9 +289,13 @@ struct yr_amd_scanner {
   // chained strings (yr_amd_scanner_set_chains; matches.h ChainParams): one
   // workspace, laid out per call by match_device_hex
   bool chains = false;
-  // alternation strings (yr_amd_scanner_set_alternations; matches.h AltParams):
-  // [1 + cap]: the queue's length, the queued records
+  // alternation strings (yr_amd_scanner_set_alternations; matches.h AltParams).
+  // d_aqueue is laid out per call as d_wqueue is, within aqueue_cap words:
+  // single block [1 + cap]: the queue's length, the queued records;
+  // batch [1 + 2 cap]: the length, the queued records, their buffers (qbuf)
   bool alternations = false;
+  // the batch's own setting (yr_amd_scanner_set_batch_alternations; matches.h BatchAltParams)
+  bool batch_alternations = false;
   uint32_t* d_aqueue = nullptr;
   size_t aqueue_cap = 0;
   uint64_t* d_chain_ws = nullptr;
@@ -2864,12 +2868,16 @@ namespace {
 // chains: the records of settled chains become events, grouped by (buffer,
 // chain) and replayed a wave per group (matches.h BatchChainParams), all of it
 // queued ahead of the first wait -- the same two waits.
+// alts: the records of alternation strings are queued with their buffers and
+// measured one wave each (matches.h BatchAltParams), beside the wide path's
+// queue when that is on -- the same two waits.
 inline uint32_t batch_chain_waves(const yr_amd_tables* t) {
   return 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
 }
 
 int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n,
-                           uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni, bool chains) {
+                           uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni, bool chains,
+                           bool alts) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
   const size_t noff = (size_t)nbuf + 1;
@@ -2950,17 +2958,20 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   // records given up on for width are queued with their buffers and measured one
   // wave each, the queue's length not waited for; should it pass the capacity,
   // the wait below sees that and the pass runs again with a larger queue.
+  // alts: the records of alternation strings go the same way through a queue of
+  // pairs of their own (BatchAltParams); the one loop serves both queues.
   const bool wide = s->batch_hex_wide;
   const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
   BatchHexWideParams bw{};
-  uint64_t queued = 0;
+  BatchAltParams ba{};
+  uint64_t queued = 0, alt_queued = 0;
   // (the inverse of the layout [1 + 2 qcap]: a capacity that holds the queue reallocates nothing)
-  for (size_t qcap = std::max<size_t>((s->wqueue_cap > 0 ? s->wqueue_cap - 1 : 0) / 2, 256);;
-       qcap = std::max<size_t>(queued, 2 * qcap)) {
-    if (wide) {
+  size_t aqcap = std::max<size_t>((s->aqueue_cap > 0 ? s->aqueue_cap - 1 : 0) / 2, 256);
+  for (size_t qcap = std::max<size_t>((s->wqueue_cap > 0 ? s->wqueue_cap - 1 : 0) / 2, 256);;) {
+    if (wide || alts) {   // (alts alone: the wide queue stays empty, the per-record counts are used)
       qcap = std::min<size_t>(qcap, kMatchMaxRecords);
       r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + 2 * qcap);   // the length, the records, their buffers
-      if (!r) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
+      if (!r && wide) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
       if (!r) r = grow_geo(s->d_wcount, s->wcount_cap, 2 * n);
       if (r) return r;
       bw.w.h = b.h;
@@ -2979,9 +2990,24 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
       bw.qbuf = s->d_wqueue + 1 + qcap;
       bw.item_off = b.item_off;
     }
+    if (alts) {
+      aqcap = std::min<size_t>(aqcap, kMatchMaxRecords);
+      r = grow_geo(s->d_aqueue, s->aqueue_cap, 1 + 2 * aqcap);   // the length, the records, their buffers
+      if (r) return r;
+      ba.b = bw;
+      ba.t = t->d_alt;
+      ba.qlen = s->d_aqueue;
+      ba.queue = s->d_aqueue + 1;
+      ba.qbuf = s->d_aqueue + 1 + aqcap;
+      ba.qcap = (uint32_t)aqcap;
+      ba.qlen_out = s->d_mhsum + 6;
+      ba.wide = wide ? 1u : 0u;
+    }
     // measure -> the offsets of the rest and of the items -> the rest, its CSR
     // and the items' CSR; wait
-    if (wide)
+    if (alts)
+      HIP_TRY(launch_batch_alt_measure(ba, wide_waves, s->stream));
+    else if (wide)
       HIP_TRY(launch_batch_hex_wide_measure(bw, wide_waves, s->stream));
     else
       HIP_TRY(launch_batch_hex_measure(b, s->stream));
@@ -3004,7 +3030,7 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
                                  s->stream));
     HIP_TRY(launch_match_rest(m, s->stream));
     HIP_TRY(launch_batch_match_offsets(rp, 0, s->stream));
-    if (wide)
+    if (wide || alts)
       HIP_TRY(launch_batch_hex_wide_offsets(bw, s->stream));
     else
       HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
@@ -3017,13 +3043,19 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
                            hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     queued = wide ? s->h_msum[4] : 0;
-    if (queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
-    if (!wide || queued <= bw.w.qcap) break;
+    alt_queued = alts ? s->h_msum[6] : 0;
+    if (queued > n || alt_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    // a queue that overflowed grows to what was appended, and the pass runs again
+    const bool wide_over = wide && queued > bw.w.qcap, alt_over = alts && alt_queued > ba.qcap;
+    if (!wide_over && !alt_over) break;
+    if (wide_over) qcap = std::max<size_t>(queued, 2 * qcap);
+    if (alt_over) aqcap = std::max<size_t>(alt_queued, 2 * aqcap);
   }
   *nr = s->h_msum[0];
   const uint64_t hex_items = s->h_msum[3];
   *nm = 0;
-  // (a record of the wave-wide path is up to YR_RE_SCAN_LIMIT + 1 items)
+  // (a record of the wave-wide path is up to YR_RE_SCAN_LIMIT + 1 items, an
+  // alternation record at most 64)
   if (*nr > n || hex_items > (wide ? (uint64_t)kReScanLimit + 1 : 64) * (n - *nr) ||
       s->h_mrest_off[nbuf] != *nr)
     return YR_AMD_INTERNAL_FATAL_ERROR;
@@ -3035,6 +3067,9 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   if (debug_level() >= 1 && wide)
     fprintf(stderr, "- %llu verify calls, %llu queued for the wave-wide path // yr_amd_match_batch_device()\n",
             (unsigned long long)n, (unsigned long long)queued);
+  if (debug_level() >= 1 && alts)
+    fprintf(stderr, "- %llu verify calls, %llu queued as alternation records // yr_amd_match_batch_device()\n",
+            (unsigned long long)n, (unsigned long long)alt_queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   if (items == 0) return YR_AMD_SUCCESS;
   r = ensure_match_workspace(s, items);
@@ -3056,7 +3091,7 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort by (buffer, string, offset); distinct (buffer, key) -> their
   // offsets -> the matches and their CSR; wait
-  if (wide) {
+  if (wide || alts) {
     bw.w.h = b.h;
     HIP_TRY(launch_hex_wide_expand(bw.w, wide_waves, s->stream));
   } else {
@@ -3111,6 +3146,12 @@ int yr_amd_scanner_set_batch_chains(yr_amd_scanner* s, int enable) {
   return YR_AMD_SUCCESS;
 }
 
+int yr_amd_scanner_set_batch_alternations(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->batch_alternations = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* s, uint32_t* waves) {
   if (s == nullptr || waves == nullptr) return YR_AMD_INVALID_ARGUMENT;
   *waves = batch_chain_waves(s->tables);
@@ -3131,6 +3172,9 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   // behind the records' measure pass, so chains take the hex driver
   if (s->batch_chains && !t->has_chains) return YR_AMD_INVALID_ARGUMENT;
   const bool chains = s->batch_chains && t->d_chain.n_chains > 0;
+  // alternation strings (yr_amd_scanner_set_batch_alternations): with the hex
+  // class only, whose refusal above covers tables without programs
+  const bool alts = hex && s->batch_alternations && t->n_alt_strings > 0;
   const yr_amd_verify_rec* d_rec = nullptr;
   const uint64_t* rec_off = nullptr;
   int r = yr_amd_verify_batch_device(s, bases, &d_rec, &rec_off);
@@ -3142,7 +3186,7 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   s->h_mrest_off.assign((size_t)nbuf + 1, 0);
   uint64_t nm = 0, nr = 0, ni = 0;
   if (n > 0 && (hex || chains)) {
-    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni, chains);
+    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni, chains, alts);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n, nbuf);
@@ -3231,6 +3275,7 @@ int yr_amd_scan_batch_matches(yr_amd_scanner* s, const uint8_t* const* data, con
                               const uint64_t** match_off, const yr_amd_verify_rec** rest,
                               const uint64_t** rest_off) {
   if (s == nullptr || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
+  // (yr_amd_scanner_set_batch_alternations too: it is read with the hex class only)
   if ((s->batch_match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
     return YR_AMD_INVALID_ARGUMENT;
   if (s->batch_chains && !s->tables->has_chains) return YR_AMD_INVALID_ARGUMENT;
