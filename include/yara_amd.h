@@ -765,6 +765,56 @@ int yr_amd_tables_alternation_strings(
 int yr_amd_scanner_set_alternations(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
 
 /*
+ * Loop strings: ordinary text regexps with * or + and no counters --
+ * /[a-z]+\.php/, /Content-Type: [a-z]+\/[a-z]+/, /x.*y/ -- settled by the match
+ * stage too.  A setting of its own beside yr_amd_scanner_set_alternations; no
+ * string is both an alternation string and a loop string.
+ *
+ * yr_amd_tables_loop_strings: out[k] = 1 iff string k is a loop string.  The
+ * preconditions of yr_amd_tables_alternation_strings.  String k is one when
+ *   1. its flags pass rule 1 of the alternation strings;
+ *   2. it has a pool entry, every pool entry of it has a forward program, and in
+ *      each program (forward, and backward where present) every instruction
+ *      reachable from the entry is one of ANY, LITERAL, NOT_LITERAL,
+ *      MASKED_LITERAL, MASKED_NOT_LITERAL, CLASS, \w \W \s \S \d \D, SPLIT_A,
+ *      SPLIT_B, JUMP, MATCH -- targets in either direction; at most 64
+ *      instructions are reachable; no split id names two instructions; no
+ *      cycle consists of SPLIT / JUMP edges alone (every loop consumes a byte:
+ *      /(a*)*b/ is out);
+ *   3. at least one of its programs has a backward edge (else it is an
+ *      alternation string or nothing);
+ *   4. resting x (splits + 1) -- resting: the byte tests and MATCH -- a bound
+ *      on the fibers yr_re_exec can hold, is below
+ *      RE_MAX_FIBERS.
+ * REPEAT_START / _END ({n,m} on anything but .), REPEAT_ANY, \b \B ^ $,
+ * nocase, wide, fullword, xor and chain parts stay with the host verifier.
+ *
+ * yr_amd_scanner_set_loops(1): yr_amd_match_device and
+ * yr_amd_scan_block_matches also settle the records of loop strings, over
+ * runs of up to YR_RE_SCAN_LIMIT bytes either way: the forward length is the
+ * bytes_matched of yr_re_exec's highest-priority path to MATCH (greedy the
+ * longest, ungreedy the shortest), every bytes_matched B of the backward
+ * program at MATCH is a match {offset - B, B + F}.  Across records scan.c:756
+ * holds: of several records with one (string, offset) the first supplies
+ * length and pool_index, but for a string with STRING_FLAGS_GREEDY_REGEXP the
+ * LAST does (/x.*\.php/ on "x.php.php": one match of length 9).  A record
+ * stays in the rest, never out as a guess, when no path reaches MATCH, when
+ * its backward results span 64 positions or more, or when, after
+ * yr_amd_scan_window, a byte either run may read lies outside the window.
+ * Read as yr_amd_scanner_set_alternations is: with YR_AMD_MATCH_HEX among the
+ * classes only, never by the batch calls; with it off, or on tables without a
+ * loop string, the calls launch what they launched before.  NULL scanner or a
+ * value other than 0/1: YR_AMD_INVALID_ARGUMENT.  The library also exports
+ * yr_amd__loop_program (conditions 2 and 4 on one program, for tests), which
+ * is no part of the interface.
+ */
+int yr_amd_tables_loop_strings(
+    const yr_amd_tables* tables,
+    uint8_t* out,
+    uint32_t n_strings);
+int yr_amd_scanner_set_loops(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
+
+/*
  * ---- Batched scans: many independent buffers in one launch ----
  *
  * Every call above takes one block and pays its fixed cost -- a scan launch in

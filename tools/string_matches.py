@@ -1,6 +1,6 @@
 """Which literal strings of a compiled rules file match where in a file.
 
-    python tools/string_matches.py [--hex | --hex-wide] [--chains] [--alternations] RULES.yarc FILE [FILE ...]
+    python tools/string_matches.py [--hex | --hex-wide] [--chains] [--alternations] [--loops] RULES.yarc FILE [FILE ...]
 
 Prints one "string offset length xor" line per match of a final string
 (include/yara_amd.h: literal, not a chain part, not base64) -- absolute file
@@ -47,6 +47,10 @@ reference takes from its list's order.
 block path (yr_amd_scanner_set_alternations): hex strings with alternatives,
 { E8 ?? ?? ?? ?? ( 5B | 5D ) C3 }, and regexps without * and +.  The batches
 several files go through do not have it: their calls stay in the count on stderr.
+
+--loops: with --hex or --hex-wide, the loop strings too on the block path
+(yr_amd_scanner_set_loops): text regexps with * and +, /[a-z]+\\.php/, runs up to
+YR_RE_SCAN_LIMIT bytes.  The batches do not have it.
 
 --chains: the chained hex strings too (yr_amd_scanner_set_chains): a hex string
 that libyara split at a jump wider than 200 bytes is printed as matches of its
@@ -106,10 +110,11 @@ def arenas(sizes):
 
 
 def main():
-    argv = [a for a in sys.argv[1:] if a not in ("--hex", "--hex-wide", "--chains", "--alternations")]
+    argv = [a for a in sys.argv[1:] if a not in ("--hex", "--hex-wide", "--chains", "--alternations", "--loops")]
     hex_class = "--hex" in sys.argv[1:] or "--hex-wide" in sys.argv[1:]
     chains = "--chains" in sys.argv[1:]
     alternations = "--alternations" in sys.argv[1:]
+    loops = "--loops" in sys.argv[1:]
     hex_wide = "--hex-wide" in sys.argv[1:]
     if len(argv) < 2:
         sys.exit(__doc__)
@@ -126,6 +131,7 @@ def main():
     sc.set_batch_hex_wide(hex_wide)
     sc.set_chains(chains)
     sc.set_alternations(alternations)
+    sc.set_loops(loops)
     sc.set_batch_chains(chains)
     paths = argv[1:]
     if len(paths) == 1:

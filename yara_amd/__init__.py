@@ -173,6 +173,18 @@ class Tables:
                        self._h, out.ctypes.data_as(_lib._u8p), n))
         return out[:n].astype(bool)
 
+    def loop_strings(self):
+        """bool[n_strings]: the strings ``Scanner.set_loops`` settles
+        (yr_amd_tables_loop_strings): text regexps with * or + whose programs
+        are byte tests, SPLIT, JUMP and MATCH.  Disjoint from
+        ``alternation_strings``; the tables need their programs."""
+        n = self.string_count()
+        out = np.zeros(max(n, 1), np.uint8)
+        _lib.check("yr_amd_tables_loop_strings",
+                   _lib.lib().yr_amd_tables_loop_strings(
+                       self._h, out.ctypes.data_as(_lib._u8p), n))
+        return out[:n].astype(bool)
+
     def _set_host_programs(self, pool_string, fwd_off, fwd_len, bwd_off, bwd_len, code):
         # host-only tables: the programs for alternation_strings
         arrs = [_arr(a, np.uint32) for a in (pool_string, fwd_off, fwd_len, bwd_off, bwd_len)]
@@ -331,6 +343,7 @@ class Scanner:
         self._batch_chains = False   # set_batch_chains
         self._chains = False   # set_chains
         self._alternations = False   # set_alternations
+        self._loops = False   # set_loops
         self._batch_alternations = False   # set_batch_alternations
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
@@ -434,12 +447,23 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_alternations(self._h, int(enable)))
         self._alternations = bool(enable)
 
-    def _with_hex(self, hex, call, wide=False, chains=False, alternations=False):
+    def set_loops(self, enable: bool):
+        """Settle loop strings too (yr_amd_scanner_set_loops): the strings
+        ``Tables.loop_strings`` names, runs up to YR_RE_SCAN_LIMIT bytes.  Read
+        only while the classes include MATCH_HEX; the batch calls never read
+        it."""
+        _lib.check("yr_amd_scanner_set_loops",
+                   _lib.lib().yr_amd_scanner_set_loops(self._h, int(enable)))
+        self._loops = bool(enable)
+
+    def _with_hex(self, hex, call, wide=False, chains=False, alternations=False, loops=False):
         # hex=True: this call with the hex class added (wide=True: and the
         # wave-wide path on; chains=True: and chained strings settled;
-        # alternations=True: and alternation strings settled), the scanner's
-        # settings restored
+        # alternations=True: and alternation strings settled; loops=True: and
+        # loop strings settled), the scanner's settings restored
         was, was_wide = self._classes, self._hex_wide
+        if not loops or self._loops:
+            loops = False
         if not alternations or self._alternations:
             alternations = False
         if not hex or (was & MATCH_HEX):
@@ -456,9 +480,13 @@ class Scanner:
             self.set_chains(True)
         if alternations:
             self.set_alternations(True)
+        if loops:
+            self.set_loops(True)
         try:
             return call()
         finally:
+            if loops:
+                self.set_loops(False)
             if alternations:
                 self.set_alternations(False)
             if chains:
@@ -548,7 +576,7 @@ class Scanner:
                 self.set_batch_match_classes(was)
 
     def match_device(self, data_base: int = 0, hex: bool = False, wide: bool = False,
-                     chains: bool = False, alternations: bool = False):
+                     chains: bool = False, alternations: bool = False, loops: bool = False):
         """(matches, rest) of the last completed device scan (yr_amd_match_device),
         copied to the host: ``matches`` {offset, string, length, xor_key,
         pool_index}, one per distinct (string, offset) of the final strings
@@ -566,9 +594,11 @@ class Scanner:
         call (set_chains): the heads' matches join ``matches``, the events of
         settled, clean chains leave ``rest``.  ``alternations=True`` settles
         the alternation strings for this call (set_alternations;
-        Tables.alternation_strings); like ``wide`` it goes with the hex class."""
+        Tables.alternation_strings); like ``wide`` it goes with the hex class.
+        ``loops=True`` does the same for the loop strings (set_loops;
+        Tables.loop_strings)."""
         return self._with_hex(hex, lambda: self._match_device(data_base), wide, chains,
-                              alternations)
+                              alternations, loops)
 
     def _match_device(self, data_base):
         from ._hip import memcpy
@@ -586,13 +616,14 @@ class Scanner:
         return matches, rest
 
     def string_matches(self, data: np.ndarray, data_base: int = 0, hex: bool = False,
-                       wide: bool = False, chains: bool = False, alternations: bool = False):
+                       wide: bool = False, chains: bool = False, alternations: bool = False,
+                       loops: bool = False):
         """(matches, rest) of a block in host memory (yr_amd_scan_block_matches):
         see match_device.  For the final strings ``matches`` is what stock
         libyara's match lists hold after scanning this block alone; the blocks
         of one scan merge with ``merge_matches``."""
         return self._with_hex(hex, lambda: self._string_matches(data, data_base), wide, chains,
-                              alternations)
+                              alternations, loops)
 
     def _string_matches(self, data, data_base):
         d = _arr(data, np.uint8)

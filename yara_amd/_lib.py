@@ -175,6 +175,8 @@ PROTOTYPES = {
     "yr_amd_scanner_set_chains": (_int, [_vp, _int]),
     "yr_amd_tables_alternation_strings": (_int, [_vp, _u8p, ctypes.c_uint32]),
     "yr_amd_scanner_set_alternations": (_int, [_vp, _int]),
+    "yr_amd_tables_loop_strings": (_int, [_vp, _u8p, ctypes.c_uint32]),
+    "yr_amd_scanner_set_loops": (_int, [_vp, _int]),
     "yr_amd_scanner_set_batch_hex_wide": (_int, [_vp, _int]),
     "yr_amd_scanner_set_batch_chains": (_int, [_vp, _int]),
     "yr_amd_scanner_batch_chain_waves": (_int, [_vp, _u32p]),

@@ -357,6 +357,58 @@ hipError_t launch_batch_alt_measure(const BatchAltParams& a, uint32_t waves, hip
 // launcher: one wave per queued wide pair.
 hipError_t launch_batch_hex_wide_waves(const BatchHexWideParams& p, uint32_t waves, hipStream_t s);
 
+// One wave per queued alternation record on its own (alt_measure_kernel), for
+// a driver that runs a measure pass with more queues (loops.hip).
+hipError_t launch_alt_waves(const AltParams& a, uint32_t waves, hipStream_t s);
+
+// ---- Loop strings (yr_amd_scanner_set_loops; loops.hip) ----
+// A text regexp with * or + and no counters: byte tests, SPLIT, JUMP, MATCH,
+// at least one backward edge, every cycle through a byte test.  A fiber is
+// its instruction, so yr_re_exec's list at input position b is a set of at
+// most 64 instructions, one 64-bit word: the wave keeps one word PER POSITION
+// (0 .. YR_RE_SCAN_LIMIT) in LDS where the alternation kernels keep one
+// 64-position word per instruction.  Instructions are AltInsn (kAltRepeat
+// never occurs, next / target are indices in either direction, a CLASS keeps
+// its `negated` in flag and its bitmap's index in a | b << 16); masks holds per
+// instruction {eps, succ}: eps the RESTING instructions (byte tests, MATCH)
+// reachable over SPLIT / JUMP edges alone (the instruction itself if it
+// rests), succ = eps[next] of a byte test, else 0.
+constexpr uint32_t kLoopPositions = 4097;   // bytes_matched 0 .. YR_RE_SCAN_LIMIT
+constexpr uint32_t kLoopClassWords = 8;
+constexpr uint8_t kLoopString = 1, kLoopGreedy = 2;   // str_loop bits
+struct LoopTables {
+  const AltProg* progs;         // [n_pool] n_fwd 0: not a loop string's entry
+  const AltInsn* insns;
+  const uint64_t* masks;        // [2 * insns] eps, succ
+  const uint32_t* classes;      // [..][kLoopClassWords]
+  const uint8_t* str_loop;      // [n_strings] kLoopString | kLoopGreedy (STRING_FLAGS_GREEDY_REGEXP)
+};
+// A struct of its own: AltParams is a kernel argument of the kernels above,
+// which stay what they are.  a.w is used either way (as AltParams uses w);
+// a.t / a.queue / a.qlen only with `alts`.
+struct LoopParams {
+  AltParams a;
+  LoopTables t;
+  uint32_t* queue;              // [qcap] the queued loop records
+  uint32_t* qlen;
+  uint32_t qcap;
+  uint64_t* qlen_out;           // qlen for the host (pinned)
+  uint32_t alts;                // alternation strings are settled too
+};
+// The measure pass with three queues: all cleared, the twin of
+// alt_measure_queue_kernel that queues loop records too, one wave per queued
+// alternation record (alts), per queued loop record, per wide record (a.wide),
+// the recount.
+hipError_t launch_loop_measure(const LoopParams& l, uint32_t waves, hipStream_t s);
+// launch_hex_unique pass 1 with scan.c:756's replace_if_exists: of the items
+// with one (string, offset) the FIRST supplies length and pool_index, but for
+// a greedy loop string the LAST.  (Pass 0 is launch_hex_unique's.)
+struct LoopUniqueParams {
+  HexMatchParams h;
+  const uint8_t* str_loop;
+};
+hipError_t launch_loop_unique(const LoopUniqueParams& u, hipStream_t s);
+
 // ---- Chained strings (yr_amd_scanner_set_chains; chains.hip) ----
 // libyara splits a hex string at every jump wider than
 // YR_STRING_CHAINING_THRESHOLD into a chain S0 <- S1 <- ... (chained_to links

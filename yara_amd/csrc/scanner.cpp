@@ -137,6 +137,12 @@ struct yr_amd_tables {
   uint32_t n_alt_strings = 0;
   uint32_t* d_alt_words = nullptr;
   AltTables d_alt{};
+  // loop strings (yr_amd_tables_loop_strings; matches.h LoopTables), decided and
+  // decoded with them: kLoopString | kLoopGreedy per string, 0: not one
+  std::vector<uint8_t> h_loop_string;
+  uint32_t n_loop_strings = 0;
+  uint32_t* d_loop_words = nullptr;
+  LoopTables d_loop{};
 };
 
 struct yr_amd_scanner {
@@ -243,7 +249,7 @@ struct yr_amd_scanner {
   size_t mhist_cap = 0;
   uint64_t* d_mhchunk = nullptr;
   size_t mhchunk_cap = 0;
-  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued, chain items, alternation records queued}
+  uint64_t* h_msum = nullptr;           // pinned, coherent: {rest records, matches, scratch, items, queued, chain items, alternation records queued, loop records queued}
   uint64_t* d_mhsum = nullptr;          // h_msum mapped for the device
   std::vector<yr_amd_match_rec> h_match;
   std::vector<yr_amd_verify_rec> h_mrest;
@@ -298,6 +304,10 @@ struct yr_amd_scanner {
   bool batch_alternations = false;
   uint32_t* d_aqueue = nullptr;
   size_t aqueue_cap = 0;
+  // loop strings (yr_amd_scanner_set_loops; matches.h LoopParams): [1 + cap], as d_aqueue
+  bool loops = false;
+  uint32_t* d_lqueue = nullptr;
+  size_t lqueue_cap = 0;
   uint64_t* d_chain_ws = nullptr;
   size_t chain_ws_cap = 0;
   // the batch's own setting (yr_amd_scanner_set_batch_chains; matches.h
@@ -503,7 +513,8 @@ int yr_amd_tables_destroy(yr_amd_tables* t) {
   if (t == nullptr) return YR_AMD_SUCCESS;
   for (void* p : {(void*)t->d_filter, (void*)t->d_exact, (void*)t->d_nodes, (void*)t->d_kc, (void*)t->d_pool,
                   (void*)t->d_str_bytes, (void*)t->d_lowercase, (void*)t->d_re_code,
-                  (void*)t->d_pool_string, (void*)t->d_chain_words, (void*)t->d_alt_words})
+                  (void*)t->d_pool_string, (void*)t->d_chain_words, (void*)t->d_alt_words,
+                  (void*)t->d_loop_words})
     if (p) (void)hipFree(p);
   delete t;
   return YR_AMD_SUCCESS;
@@ -601,7 +612,7 @@ int yr_amd_scanner_destroy(yr_amd_scanner* s) {
                   (void*)s->d_mhchunk, (void*)s->d_mbuf, (void*)s->d_moff, (void*)s->d_hkeys,
                   (void*)s->d_hmeas, (void*)s->d_hsets, (void*)s->d_hrest, (void*)s->d_hblock,
                   (void*)s->d_hchunk, (void*)s->d_wqueue, (void*)s->d_wsets, (void*)s->d_wcount,
-                  (void*)s->d_chain_ws, (void*)s->d_aqueue})
+                  (void*)s->d_chain_ws, (void*)s->d_aqueue, (void*)s->d_lqueue})
     if (p) (void)hipFree(p);
   if (s->h_msum) (void)hipHostFree(s->h_msum);
   if (s->h_arena) (void)hipHostFree(s->h_arena);
@@ -1651,8 +1662,247 @@ int attach_alternations(yr_amd_tables* t, const std::vector<uint32_t>& pool_stri
   t->d_alt.str_alt = reinterpret_cast<const uint8_t*>(d + at_str);
   return YR_AMD_SUCCESS;
 }
+
+// One program of a loop string (include/yara_amd.h yr_amd_tables_loop_strings,
+// conditions 2 and 3): every instruction reachable from the entry is a byte
+// test, SPLIT, JUMP or MATCH -- targets in either direction -- at most
+// kAltMaxInsns instructions, no split id used twice, no cycle of SPLIT / JUMP
+// edges alone, and resting x (splits + 1), the bound on the fibers yr_re_exec
+// can hold, below RE_MAX_FIBERS.  *back: it has a backward
+// edge.  The decoded instructions (matches.h LoopTables) are appended to insns,
+// their {eps, succ} to masks, the classes' bitmaps to classes.
+bool loop_program(const uint8_t* c, uint32_t len, std::vector<AltInsn>& insns, std::vector<uint64_t>& masks,
+                  std::vector<uint32_t>& classes, uint64_t* bound_out, bool* back) {
+  if (bound_out) *bound_out = 0;
+  if (back) *back = false;
+  if (len == 0) return false;
+  std::vector<uint8_t> seen(len, 0);
+  std::vector<uint32_t> work{0};
+  while (!work.empty()) {
+    uint32_t ip = work.back();
+    work.pop_back();
+    while (true) {
+      if (ip >= len) return false;
+      if (seen[ip]) break;
+      seen[ip] = 1;
+      const uint8_t op = c[ip];
+      const uint32_t sz = re_op_size(op);
+      if (sz == 0 || ip + sz > len) return false;
+      if (op == kOpMatch) break;
+      if (op == kOpJump || op == kOpSplitA || op == kOpSplitB) {
+        const int64_t to = (int64_t)ip + re_i16(c + ip + (op == kOpJump ? 1 : 2));
+        if (to < 0 || to >= (int64_t)len) return false;
+        if (to <= (int64_t)ip && back) *back = true;
+        if (op == kOpJump) {
+          ip = (uint32_t)to;
+          continue;
+        }
+        work.push_back((uint32_t)to);
+      } else if (!(op == kOpAny || op == kOpLiteral || op == kOpNotLiteral || op == kOpMaskedLiteral ||
+                   op == kOpMaskedNotLiteral || op == kOpClass || op == kOpWordChar ||
+                   op == kOpNonWordChar || op == kOpSpace || op == kOpNonSpace || op == kOpDigit ||
+                   op == kOpNonDigit)) {
+        return false;   // REPEAT_ANY (its rc is state beyond the instruction), REPEAT_START / _END, \b \B ^ $
+      }
+      ip += sz;
+    }
+  }
+  std::vector<uint32_t> addr;
+  std::vector<int32_t> index(len, -1);
+  for (uint32_t ip = 0; ip < len; ++ip)
+    if (seen[ip]) {
+      index[ip] = (int32_t)addr.size();
+      addr.push_back(ip);
+    }
+  const uint32_t n = (uint32_t)addr.size();
+  if (n > kAltMaxInsns) return false;
+  bool split_id[256] = {};
+  std::vector<AltInsn> prog(n);
+  std::vector<uint32_t> cls;
+  uint64_t resting = 0, splits = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t ip = addr[i];
+    const uint8_t op = c[ip];
+    AltInsn in{};
+    const uint32_t after = ip + re_op_size(op);
+    in.next = (op == kOpMatch || op == kOpJump) ? 0 : (uint8_t)index[after];
+    switch (op) {
+      case kOpAny: in.op = kAltAny; break;
+      case kOpLiteral: case kOpNotLiteral:
+        in.op = kAltByte; in.a = c[ip + 1]; in.b = 0xFF; in.flag = op == kOpNotLiteral; break;
+      case kOpMaskedLiteral: case kOpMaskedNotLiteral:
+        in.op = kAltByte; in.a = c[ip + 1]; in.b = c[ip + 2]; in.flag = op == kOpMaskedNotLiteral; break;
+      case kOpClass: {
+        const uint32_t k = (uint32_t)((classes.size() + cls.size()) / kLoopClassWords);
+        in.op = kAltClass; in.a = (uint16_t)k; in.b = (uint16_t)(k >> 16);
+        in.flag = c[ip + 1] != 0;   // RE_CLASS.negated
+        for (uint32_t w = 0; w < 8; ++w) cls.push_back((uint32_t)re_i32(c + ip + 2 + 4 * w));
+        break;
+      }
+      case kOpWordChar: case kOpNonWordChar: in.op = kAltWord; in.flag = op == kOpNonWordChar; break;
+      case kOpSpace: case kOpNonSpace: in.op = kAltSpace; in.flag = op == kOpNonSpace; break;
+      case kOpDigit: case kOpNonDigit: in.op = kAltDigit; in.flag = op == kOpNonDigit; break;
+      case kOpSplitA: case kOpSplitB:
+        // (the reference kills a fiber that meets a split id twice in one sync, re.c:1482-1495:
+        // harmless only where an id names one instruction)
+        if (split_id[c[ip + 1]]) return false;
+        split_id[c[ip + 1]] = true;
+        in.op = kAltSplit; in.flag = op == kOpSplitB;
+        in.target = (uint8_t)index[(int64_t)ip + re_i16(c + ip + 2)];
+        ++splits;
+        break;
+      case kOpJump: in.op = kAltJump; in.target = (uint8_t)index[(int64_t)ip + re_i16(c + ip + 1)]; break;
+      default: in.op = kAltMatch; break;
+    }
+    if (in.op <= kAltDigit || in.op == kAltMatch) ++resting;
+    prog[i] = in;
+  }
+  // eps over the SPLIT / JUMP edges, depth first; a node met again while open
+  // closes a cycle that consumes no byte: (a*)*
+  std::vector<uint64_t> eps(n, 0);
+  std::vector<uint8_t> state(n, 0);   // 1: open, 2: done
+  for (uint32_t root = 0; root < n; ++root) {
+    std::vector<uint32_t> stack{root};
+    while (!stack.empty()) {
+      const uint32_t i = stack.back();
+      const AltInsn& in = prog[i];
+      if (state[i] == 2) {
+        stack.pop_back();
+        continue;
+      }
+      if (in.op != kAltSplit && in.op != kAltJump) {
+        eps[i] = 1ull << i;
+        state[i] = 2;
+        stack.pop_back();
+        continue;
+      }
+      const uint32_t kids[2] = {in.target, in.op == kAltSplit ? in.next : in.target};
+      if (state[i] == 0) {
+        state[i] = 1;
+        for (uint32_t k : kids) {
+          if (state[k] == 1) return false;
+          if (state[k] == 0) stack.push_back(k);
+        }
+      } else {   // (open, its children done)
+        eps[i] = eps[kids[0]] | eps[kids[1]];
+        state[i] = 2;
+        stack.pop_back();
+      }
+    }
+  }
+  const uint64_t bound = std::max<uint64_t>(resting, 1) * (splits + 1);
+  if (bound_out) *bound_out = bound;
+  if (bound >= kAltFiberLimit) return false;
+  for (uint32_t i = 0; i < n; ++i) {
+    insns.push_back(prog[i]);
+    masks.push_back(eps[i]);
+    masks.push_back(prog[i].op <= kAltDigit ? eps[prog[i].next] : 0ull);
+  }
+  classes.insert(classes.end(), cls.begin(), cls.end());
+  return true;
+}
+
+// The loop class and its device tables, beside attach_alternations: the flag
+// rule is the same, the programs differ, and a string is a loop string only
+// if one of its programs has a backward edge -- so no string is in both.
+int attach_loops(yr_amd_tables* t, const std::vector<uint32_t>& pool_string, const std::vector<DevRe>& re,
+                 const uint8_t* code) {
+  const uint32_t n_strings = (uint32_t)t->h_str_flags.size(), n_pool = (uint32_t)re.size();
+  std::vector<uint8_t> loop(n_strings, 0), entries(n_strings, 0), backs(n_strings, 0);
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    const uint32_t f = t->h_str_flags[k];
+    if ((f & kStrAscii) && !(f & kAltExcluded))
+      loop[k] = kLoopString | ((f & kStrGreedyRegexp) ? kLoopGreedy : 0);
+  }
+  std::vector<AltProg> progs(n_pool, AltProg{0, 0, 0, 0, 0});
+  std::vector<AltInsn> insns;
+  std::vector<uint64_t> masks;
+  std::vector<uint32_t> classes;
+  for (uint32_t k = 0; k < n_pool; ++k) {
+    const uint32_t s = pool_string[k];
+    if (!loop[s]) continue;
+    entries[s] = 1;
+    AltProg& p = progs[k];
+    bool back = false;
+    p.fwd = (uint32_t)insns.size();
+    bool ok = re[k].fwd_len > 0 &&
+              loop_program(code + re[k].fwd_off, re[k].fwd_len, insns, masks, classes, nullptr, &back);
+    if (ok) p.n_fwd = (uint8_t)(insns.size() - p.fwd);
+    if (back) backs[s] = 1;
+    p.bwd = (uint32_t)insns.size();
+    if (ok && re[k].bwd_len > 0) {
+      ok = loop_program(code + re[k].bwd_off, re[k].bwd_len, insns, masks, classes, nullptr, &back);
+      if (ok) p.n_bwd = (uint8_t)(insns.size() - p.bwd);
+      if (back) backs[s] = 1;
+    }
+    if (!ok) loop[s] = 0;
+  }
+  t->n_loop_strings = 0;
+  for (uint32_t k = 0; k < n_strings; ++k) {
+    if (!entries[k] || !backs[k]) loop[k] = 0;   // (loop-free: an alternation string or nothing)
+    t->n_loop_strings += loop[k] != 0;
+  }
+  for (uint32_t k = 0; k < n_pool; ++k)
+    if (!loop[pool_string[k]]) progs[k].n_fwd = progs[k].n_bwd = 0;
+  t->h_loop_string = loop;
+  if (t->device < 0) return YR_AMD_SUCCESS;
+  // one allocation: masks (4 words per instruction), insns (2), progs (3 per entry), classes, str_loop
+  const size_t at_insns = 4 * insns.size(), at_progs = at_insns + 2 * insns.size();
+  const size_t at_classes = at_progs + 3 * (size_t)n_pool, at_str = at_classes + classes.size();
+  std::vector<uint32_t> w(at_str + (n_strings + 3) / 4 + 1, 0);
+  if (!insns.empty()) {
+    memcpy(w.data(), masks.data(), 8 * masks.size());
+    memcpy(w.data() + at_insns, insns.data(), 8 * insns.size());
+  }
+  if (n_pool > 0) memcpy(w.data() + at_progs, progs.data(), 12 * (size_t)n_pool);
+  if (!classes.empty()) memcpy(w.data() + at_classes, classes.data(), 4 * classes.size());
+  if (n_strings > 0) memcpy(w.data() + at_str, loop.data(), n_strings);
+  int r = upload(t->d_loop_words, w.data(), w.size());
+  if (r) {
+    if (t->d_loop_words) (void)hipFree(t->d_loop_words);
+    t->d_loop_words = nullptr;
+    return r;
+  }
+  const uint32_t* d = t->d_loop_words;
+  t->d_loop.masks = reinterpret_cast<const uint64_t*>(d);
+  t->d_loop.insns = reinterpret_cast<const AltInsn*>(d + at_insns);
+  t->d_loop.progs = reinterpret_cast<const AltProg*>(d + at_progs);
+  t->d_loop.classes = d + at_classes;
+  t->d_loop.str_loop = reinterpret_cast<const uint8_t*>(d + at_str);
+  return YR_AMD_SUCCESS;
+}
+
+// Both classes, once flags, pool strings and programs are known.
+int attach_programs(yr_amd_tables* t, const std::vector<uint32_t>& pool_string, const std::vector<DevRe>& re,
+                    const uint8_t* code) {
+  const int r = attach_alternations(t, pool_string, re, code);
+  return r ? r : attach_loops(t, pool_string, re, code);
+}
 }  // namespace
 }  // extern "C++"
+
+// Not declared in include/yara_amd.h: loop_program on one program, for the CPU
+// tests (tests/test_loops_abi.py): 1 if it is a loop string's program with a
+// fiber bound below RE_MAX_FIBERS, else 0; *bound = the bound (0: refused
+// before the bound), *back = it has a backward edge.
+int yr_amd__loop_program(const uint8_t* code, uint32_t len, uint64_t* bound, int* back) {
+  if (code == nullptr) return -1;
+  std::vector<AltInsn> insns;
+  std::vector<uint64_t> masks;
+  std::vector<uint32_t> classes;
+  bool b = false;
+  const bool ok = loop_program(code, len, insns, masks, classes, bound, &b);
+  if (back) *back = b ? 1 : 0;
+  return ok ? 1 : 0;
+}
+
+int yr_amd_tables_loop_strings(const yr_amd_tables* t, uint8_t* out, uint32_t n_strings) {
+  if (t == nullptr || !(t->has_strings || t->has_str_flags) || n_strings != t->h_str_flags.size() ||
+      (n_strings > 0 && out == nullptr) || !t->has_programs)
+    return YR_AMD_INVALID_ARGUMENT;
+  for (uint32_t k = 0; k < n_strings; ++k) out[k] = t->h_loop_string[k] != 0 ? 1 : 0;
+  return YR_AMD_SUCCESS;
+}
 
 // Not declared in include/yara_amd.h: alt_program on one program, for the CPU
 // tests (tests/test_alternation_abi.py): 1 if it is loop-free with a fiber
@@ -1686,7 +1936,7 @@ int yr_amd__tables_set_host_programs(yr_amd_tables* t, const uint32_t* pool_stri
         (uint64_t)re[k].bwd_off + re[k].bwd_len > code_len)
       return YR_AMD_INVALID_ARGUMENT;
   }
-  return attach_alternations(t, std::vector<uint32_t>(pool_string, pool_string + n_pool), re, code);
+  return attach_programs(t, std::vector<uint32_t>(pool_string, pool_string + n_pool), re, code);
 }
 
 int yr_amd_tables_alternation_strings(const yr_amd_tables* t, uint8_t* out, uint32_t n_strings) {
@@ -1792,7 +2042,7 @@ int yr_amd_tables_set_re_code(yr_amd_tables* t, uint32_t n_pool, const uint32_t*
                               hipMemcpyHostToDevice) != hipSuccess)
     return YR_AMD_INTERNAL_FATAL_ERROR;
   key_classes(t);
-  return attach_alternations(t, t->h_pool_string, re, code);
+  return attach_programs(t, t->h_pool_string, re, code);
 }
 
 int yr_amd_verify_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_verify_rec** d_records,
@@ -2051,8 +2301,10 @@ int ensure_match_workspace(yr_amd_scanner* s, uint64_t n, uint64_t nbuf = 0) {
 // the same two waits.
 // alts: the records of alternation strings are queued and measured one wave
 // each (matches.h AltParams), beside the wide path's queue when that is on.
+// loops: the same for the records of loop strings (matches.h LoopParams), a
+// third queue; the unique pass then honours replace_if_exists for them.
 int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n, uint64_t* nm,
-                     uint64_t* nr, bool chains, bool alts) {
+                     uint64_t* nr, bool chains, bool alts, bool loops) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
   // (the pinned totals; the items' arrays grow below.  With chains the events'
@@ -2127,14 +2379,17 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   const bool wide = s->hex_wide;
   const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
   AltParams a{};
-  uint64_t queued = 0, alt_queued = 0;
+  LoopParams l{};
+  uint64_t queued = 0, alt_queued = 0, loop_queued = 0;
   size_t aqcap = std::max<size_t>(s->aqueue_cap, 257) - 1;
+  size_t lqcap = std::max<size_t>(s->lqueue_cap, 257) - 1;
   for (size_t qcap = std::max<size_t>(s->wqueue_cap, 257) - 1;;) {
-    if (wide || alts) {   // (alts alone: the wide queue stays empty, the per-record counts are used)
+    if (wide || alts || loops) {   // (without wide its queue stays empty, the per-record counts are used)
       r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + qcap);
       if (!r && wide) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
       if (!r) r = grow_geo(s->d_wcount, s->wcount_cap, 2 * n);
       if (!r && alts) r = grow_geo(s->d_aqueue, s->aqueue_cap, 1 + aqcap);
+      if (!r && loops) r = grow_geo(s->d_lqueue, s->lqueue_cap, 1 + lqcap);
       if (r) return r;
       w.h = p;
       w.qlen = s->d_wqueue;
@@ -2154,8 +2409,23 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
       a.qlen_out = s->d_mhsum + 6;
       a.wide = wide ? 1u : 0u;
     }
+    if (loops) {
+      if (!alts) {
+        a.w = w;
+        a.wide = wide ? 1u : 0u;
+      }
+      l.a = a;
+      l.t = t->d_loop;
+      l.qlen = s->d_lqueue;
+      l.queue = s->d_lqueue + 1;
+      l.qcap = (uint32_t)std::min<size_t>(s->lqueue_cap - 1, kMatchMaxRecords);
+      l.qlen_out = s->d_mhsum + 7;
+      l.alts = alts ? 1u : 0u;
+    }
     // measure -> the offsets of the rest and of the items -> the rest; wait
-    if (alts)
+    if (loops)
+      HIP_TRY(launch_loop_measure(l, wide_waves, s->stream));
+    else if (alts)
       HIP_TRY(launch_alt_measure(a, wide_waves, s->stream));
     else if (wide)
       HIP_TRY(launch_hex_wide_measure(w, wide_waves, s->stream));
@@ -2187,12 +2457,15 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
     HIP_TRY(hipStreamSynchronize(s->stream));
     queued = wide ? s->h_msum[4] : 0;
     alt_queued = alts ? s->h_msum[6] : 0;
-    if (queued > n || alt_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    loop_queued = loops ? s->h_msum[7] : 0;
+    if (queued > n || alt_queued > n || loop_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
     // a queue that overflowed grows to what was appended, and the pass runs again
     const bool wide_over = wide && queued > w.qcap, alt_over = alts && alt_queued > a.qcap;
-    if (!wide_over && !alt_over) break;
+    const bool loop_over = loops && loop_queued > l.qcap;
+    if (!wide_over && !alt_over && !loop_over) break;
     if (wide_over) qcap = std::max<size_t>(queued, 2 * qcap);
     if (alt_over) aqcap = std::max<size_t>(alt_queued, 2 * aqcap);
+    if (loop_over) lqcap = std::max<size_t>(loop_queued, 2 * lqcap);
   }
   *nr = s->h_msum[0];
   const uint64_t hex_items = s->h_msum[3];
@@ -2208,6 +2481,9 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   if (debug_level() >= 1 && alts)
     fprintf(stderr, "- %llu verify calls, %llu queued as alternation records // yr_amd_match_device()\n",
             (unsigned long long)n, (unsigned long long)alt_queued);
+  if (debug_level() >= 1 && loops)
+    fprintf(stderr, "- %llu verify calls, %llu queued as loop records // yr_amd_match_device()\n",
+            (unsigned long long)n, (unsigned long long)loop_queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   *nm = 0;
   if (items == 0) return YR_AMD_SUCCESS;
@@ -2226,7 +2502,7 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   uint64_t* const keys[2] = {s->d_mkeys, s->d_mkeys + s->match_cap};
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort; distinct keys -> their offsets -> the matches; wait
-  if (wide || alts) {
+  if (wide || alts || loops) {
     w.h = p;
     HIP_TRY(launch_hex_wide_expand(w, wide_waves, s->stream));
   } else {
@@ -2248,7 +2524,10 @@ int match_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t
   HIP_TRY(launch_hex_unique(p, 0, s->stream));
   HIP_TRY(launch_block_offsets(p.ublock_off, p.uchunk_off, items, s->d_mhsum + 1, nullptr, none,
                                s->stream));
-  HIP_TRY(launch_hex_unique(p, 1, s->stream));
+  if (loops)   // (a greedy loop string's last record supplies the length: scan.c:756)
+    HIP_TRY(launch_loop_unique(LoopUniqueParams{p, t->d_loop.str_loop}, s->stream));
+  else
+    HIP_TRY(launch_hex_unique(p, 1, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   *nm = s->h_msum[1];
   if (*nm > items) return YR_AMD_INTERNAL_FATAL_ERROR;
@@ -2393,6 +2672,12 @@ int yr_amd_scanner_set_alternations(yr_amd_scanner* s, int enable) {
   return YR_AMD_SUCCESS;
 }
 
+int yr_amd_scanner_set_loops(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->loops = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_match_rec** d_matches,
                         uint64_t* n_matches, const yr_amd_verify_rec** d_rest, uint64_t* n_rest) {
   if (s == nullptr || s->pending || !s->scanned || s->batch || !s->tables->has_strings)
@@ -2421,8 +2706,10 @@ int yr_amd_match_device(yr_amd_scanner* s, uint64_t data_base, const yr_amd_matc
   uint64_t nm = 0, nr = 0;
   // alternation strings (yr_amd_scanner_set_alternations): with the hex class only
   const bool alts = hex && s->alternations && t->n_alt_strings > 0;
+  // loop strings (yr_amd_scanner_set_loops): the same
+  const bool loops = hex && s->loops && t->n_loop_strings > 0;
   if (n > 0 && (hex || chains)) {   // (the events are assembled behind the records' measure pass)
-    r = match_device_hex(s, d_rec, n, &nm, &nr, chains, alts);
+    r = match_device_hex(s, d_rec, n, &nm, &nr, chains, alts, loops);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n);
