@@ -802,7 +802,8 @@ int yr_amd_scanner_set_alternations(yr_amd_scanner* scanner, int enable); /* 0 d
  * its backward results span 64 positions or more, or when, after
  * yr_amd_scan_window, a byte either run may read lies outside the window.
  * Read as yr_amd_scanner_set_alternations is: with YR_AMD_MATCH_HEX among the
- * classes only, never by the batch calls; with it off, or on tables without a
+ * classes only, never by the batch calls (theirs is
+ * yr_amd_scanner_set_batch_loops below); with it off, or on tables without a
  * loop string, the calls launch what they launched before.  NULL scanner or a
  * value other than 0/1: YR_AMD_INVALID_ARGUMENT.  The library also exports
  * yr_amd__loop_program (conditions 2 and 4 on one program, for tests), which
@@ -1173,6 +1174,40 @@ int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* scanner, uint32_t* wa
  * queue).  NULL scanner or a value other than 0/1: YR_AMD_INVALID_ARGUMENT.
  */
 int yr_amd_scanner_set_batch_alternations(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
+
+/*
+ * The batch's loop strings.  0 (default): every record of a loop string of a
+ * batch stays in the rest, and the batch stage launches exactly what it
+ * launches without this setting.  1: yr_amd_match_batch_device and
+ * yr_amd_scan_batch_matches (and through them gathered batches) also settle
+ * the records of the strings yr_amd_tables_loop_strings names, per buffer, as
+ * yr_amd_scanner_set_loops does for a single block.  Read only by the batch
+ * match calls, and only when the BATCH classes include YR_AMD_MATCH_HEX; the
+ * single-block calls never read it, and the batch calls still never read
+ * yr_amd_scanner_set_loops.
+ *
+ * With the setting on, buffer k of a batch gets exactly the matches and the
+ * rest that yr_amd_scan_block_matches(data_k, size_k, bases[k]) returns for
+ * that buffer alone on a scanner with yr_amd_scanner_set_loops(1) and the same
+ * classes, wide, chains and alternations settings:
+ *   - the buffer is the whole block of both runs: max_bytes_matched is
+ *     min(size_k - local offset, YR_RE_SCAN_LIMIT) forwards and min(local
+ *     offset, YR_RE_SCAN_LIMIT) backwards, and no byte of a gap or of a
+ *     neighbouring buffer is read -- a batch buffer is never a window;
+ *   - one entry per (buffer, string, local offset); a greedy string's LAST
+ *     record in record order supplies length and pool_index, every other
+ *     string's first (scan.c:756), and two buffers never share an entry;
+ *   - a record stays in the rest, in place, when no path reaches MATCH or when
+ *     its backward results span 64 positions or more.
+ * With the setting on and tables without programs the batch match calls return
+ * YR_AMD_INVALID_ARGUMENT (as they do for the hex class),
+ * yr_amd_scan_batch_matches before any copy.  The stage still waits twice;
+ * should the records outgrow the device queue, the first wait sees it, the
+ * queue grows and the measure pass runs again (one loop with the wide path's
+ * and the alternation strings' queues).  NULL scanner or a value other than
+ * 0/1: YR_AMD_INVALID_ARGUMENT.
+ */
+int yr_amd_scanner_set_batch_loops(yr_amd_scanner* scanner, int enable); /* 0 default; 0/1 only */
 
 /*
  * ---- Block pipeline ----

@@ -58,6 +58,15 @@ With --parent-tree the setting is left off and the same calls are timed on this
 tree's library and on another build's (the parent commit's), one child process
 each, alternating --rounds times: the idle cost of the change next to the
 run-to-run spread the same runs show.
+
+    python tools/batch_match_rate.py --loops [--reps 10] [--parent-tree DIR --rounds 5]
+                                     [--out profiles/batch_loop_match_rates.json]
+
+The batch's loop strings (yr_amd_scanner_set_batch_loops) in the same way, with a
+third workload of 262,144 x 1 KiB (the loop waves' table is sized to the largest
+buffer) and a second input: 65,536 `Rn6!a..z` records of the loops fixture's
+`run` string (tools/match_rate.py planted_runs) under that fixture's tables, as
+1 KiB and as 4 KiB buffers -- a queue 32 times the fixed grid at two table sizes.
 """
 import argparse
 import ctypes
@@ -281,7 +290,7 @@ def hex_wide_leg(a):
             f.write("\n")
 
 
-def alternations_leg(a):
+def alternations_leg(a, mode="alternations"):
     import subprocess
     med = lambda v: round(statistics.median(v), 4)   # noqa: E731
     span = lambda v: [round(min(v), 4), round(max(v), 4)]   # noqa: E731
@@ -295,7 +304,7 @@ def alternations_leg(a):
                 env = dict(os.environ)
                 if lib:
                     env["YARA_AMD_PACKAGE_ROOT"] = lib
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--alternations", "--child",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--" + mode, "--child",
                                     "--reps", str(a.reps), "--scale", str(a.scale), "--buffers",
                                     str(a.buffers)], env=env, capture_output=True, text=True, timeout=300)
                 if r.returncode != 0:   # (nothing more is started on the device)
@@ -320,62 +329,74 @@ def alternations_leg(a):
         import planted
         L = _lib.lib()
         stream = torch.cuda.Stream()
-        t = yara_amd.Tables.from_npz(os.path.join(REPO, "tests", "golden", "tables", "rx.npz"), strings=True)
-        host = planted.rx_buffer(oracle.xorshift, total, 19)   # (rx_1M's generator at this size)
-        buf = torch.empty(total + 16, dtype=torch.uint8, device="cuda")
-        buf[:total] = torch.from_numpy(host).cuda()
-        torch.cuda.synchronize()
+        golden = os.path.join(REPO, "tests", "golden")
         out = {"bytes": total, "reps": a.reps, "classes": "LITERAL | HEX", "input": "rx planted", "runs": []}
         child = {}
-        for n, size in WORKLOADS:
-            if a.buffers and n != a.buffers:
-                continue
-            n = total // size
-            sizes = np.full(n, size, np.uint64)
-            starts = np.arange(n, dtype=np.uint64) * np.uint64(size)
-            sc = yara_amd.Scanner(t, stream=stream.cuda_stream)
-            sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
-            sc.scan_batch_device(buf.data_ptr(), total, starts, sizes)
-            sc.batch_result()
-            p1, p2 = ctypes.c_void_p(), ctypes.c_void_p()
-            o1, o2 = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+        # (input, tables, its bytes, the buffer sizes it is cut into)
+        legs = [("rx planted", os.path.join(golden, "tables", "rx.npz"),
+                 lambda: planted.rx_buffer(oracle.xorshift, total, 19),   # (rx_1M's generator at this size)
+                 [size for _, size in WORKLOADS] + ([1 << 10] if mode == "loops" and not a.child else []))]
+        if mode == "loops" and not a.child:
+            from match_rate import planted_runs
+            legs.append(("65536 planted Rn6!a..z records", os.path.join(golden, "loops", "tables.npz"),
+                         lambda: planted_runs(65536)[:65536 * 16], [1 << 10, 4 << 10]))
+        for name, path, make, cuts in legs:
+            t = yara_amd.Tables.from_npz(path, strings=True)
+            host = make()
+            nbytes = host.size
+            buf = torch.empty(nbytes + 16, dtype=torch.uint8, device="cuda")
+            buf[:nbytes] = torch.from_numpy(host).cuda()
+            torch.cuda.synchronize()
+            for size in cuts:
+                n = nbytes // size
+                if a.buffers and dict(WORKLOADS).get(a.buffers) != size:
+                    continue
+                sizes = np.full(n, size, np.uint64)
+                starts = np.arange(n, dtype=np.uint64) * np.uint64(size)
+                sc = yara_amd.Scanner(t, stream=stream.cuda_stream)
+                sc.set_batch_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+                sc.scan_batch_device(buf.data_ptr(), nbytes, starts, sizes)
+                sc.batch_result()
+                p1, p2 = ctypes.c_void_p(), ctypes.c_void_p()
+                o1, o2 = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
 
-            def stage(on):   # (ms, matches, rest): the device call alone
-                if on is not None:
-                    sc.set_batch_alternations(on)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                _lib.check("yr_amd_match_batch_device", L.yr_amd_match_batch_device(
-                    sc._h, None, ctypes.byref(p1), ctypes.byref(o1), ctypes.byref(p2), ctypes.byref(o2)))
-                e1.record(stream)
-                e1.synchronize()
-                return e0.elapsed_time(e1), int(o1[n]), int(o2[n])
+                def stage(on):   # (ms, matches, rest): the device call alone
+                    if on is not None:
+                        getattr(sc, "set_batch_" + mode)(on)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    _lib.check("yr_amd_match_batch_device", L.yr_amd_match_batch_device(
+                        sc._h, None, ctypes.byref(p1), ctypes.byref(o1), ctypes.byref(p2), ctypes.byref(o2)))
+                    e1.record(stream)
+                    e1.synchronize()
+                    return e0.elapsed_time(e1), int(o1[n]), int(o2[n])
 
-            if a.child:   # the setting is never touched: the same calls on either library
-                for _ in range(3):
-                    stage(None)
-                child["%dx%d" % (n, size)] = med([stage(None)[0] for _ in range(a.reps)])
+                if a.child:   # the setting is never touched: the same calls on either library
+                    for _ in range(3):
+                        stage(None)
+                    child["%dx%d" % (n, size)] = med([stage(None)[0] for _ in range(a.reps)])
+                    sc.close()
+                    continue
+                for _ in range(2):   # warm-up: buffers and the queue grown, clocks up
+                    stage(False)
+                    stage(True)
+                ms, count = {False: [], True: []}, {}
+                for _ in range(a.reps):   # alternating
+                    for on in (False, True):
+                        v, m, r = stage(on)
+                        ms[on].append(v)
+                        count[on] = (m, r)
+                run = {"input": name, "buffers": n, "buffer_bytes": size,
+                       "records": int(sc.verify_batch_device()[1][-1]),
+                       "off": {"matches": count[False][0], "rest": count[False][1],
+                               "match_batch_ms": med(ms[False]), "min_max_ms": span(ms[False])},
+                       "on": {"matches": count[True][0], "rest": count[True][1],
+                              "match_batch_ms": med(ms[True]), "min_max_ms": span(ms[True])},
+                       "added_ms": round(med(ms[True]) - med(ms[False]), 4),
+                       mode[:-1] + "_records": count[False][1] - count[True][1]}
+                out["runs"].append(run)
+                print(json.dumps(run), flush=True)
                 sc.close()
-                continue
-            for _ in range(2):   # warm-up: buffers and the queue grown, clocks up
-                stage(False)
-                stage(True)
-            ms, count = {False: [], True: []}, {}
-            for _ in range(a.reps):   # alternating
-                for on in (False, True):
-                    v, m, r = stage(on)
-                    ms[on].append(v)
-                    count[on] = (m, r)
-            run = {"buffers": n, "buffer_bytes": size, "records": int(sc.verify_batch_device()[1][-1]),
-                   "off": {"matches": count[False][0], "rest": count[False][1],
-                           "match_batch_ms": med(ms[False]), "min_max_ms": span(ms[False])},
-                   "on": {"matches": count[True][0], "rest": count[True][1],
-                          "match_batch_ms": med(ms[True]), "min_max_ms": span(ms[True])},
-                   "added_ms": round(med(ms[True]) - med(ms[False]), 4),
-                   "alternation_records": count[False][1] - count[True][1]}
-            out["runs"].append(run)
-            print(json.dumps(run), flush=True)
-            sc.close()
         if a.child:
             print(json.dumps({"off_ms": child}), flush=True)
             return
@@ -399,15 +420,18 @@ def main():
                     help="the batch's wave-wide path, off against on (see above)")
     ap.add_argument("--alternations", action="store_true",
                     help="the batch's alternation strings, off against on, on rx's planted input")
+    ap.add_argument("--loops", action="store_true",
+                    help="the batch's loop strings, off against on, on rx's planted input and on "
+                         "planted records of the loops fixture's `run` string")
     ap.add_argument("--parent-tree", default=None,
-                    help="with --alternations: a directory holding another build's yara_amd package "
+                    help="with --alternations or --loops: a directory holding another build's yara_amd package "
                          "(the parent commit's, with its library) to time the setting off against, "
                          "alternating child processes")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.alternations:
-        return alternations_leg(a)
+    if a.alternations or a.loops:
+        return alternations_leg(a, "loops" if a.loops else "alternations")
     if a.hex_wide:
         return hex_wide_leg(a)
     if a.hex:

@@ -47,6 +47,13 @@ setting is left off and the same calls are timed on this tree's library and on
 another build's (the parent commit's), one child process each, alternating
 --rounds times: the idle cost of the change next to the run-to-run spread the
 same runs show.
+
+    python tools/match_rate.py --loops [--gib 1] [--reps 10] [--out profiles/loop_match_rates.json]
+
+Loop strings (yr_amd_scanner_set_loops) in the same way, on two inputs: rx's
+planted input under rx's tables (its string 4 is a loop string), and 65,536
+`Rn6!a..z` records, one every 16 bytes of 1 MiB of zeros, under the tables of
+tests/golden/loops -- a queue 32 times the fixed grid, every record settled.
 """
 import argparse
 import json
@@ -225,9 +232,21 @@ def hex_wide_leg(a):
             f.write("\n")
 
 
-def alternations_leg(a):
+def planted_runs(records):
+    """`Rn6!a..z` of tests/golden/loops' string `run`, one record every 16 bytes of zeros."""
+    import numpy as np
+    buf = np.zeros(records * 16 + 64, np.uint8)
+    rows = buf[:records * 16].reshape(records, 16)
+    for k in range(7):   # Rn6! + 1..7 a + z
+        word = np.frombuffer(b"Rn6!" + b"a" * (1 + k) + b"z", np.uint8)
+        rows[k::7, 4:4 + word.size] = word
+    return buf
+
+
+def alternations_leg(a, mode="alternations"):
     """yr_amd_match_device on rx's planted input resident in HBM, classes LITERAL | HEX, the
-    alternation setting off and on, alternating.  With --parent-tree: the setting OFF on this
+    alternation setting (mode "loops": the loop setting; then a second input, planted_runs
+    under the loops fixture's tables) off and on, alternating.  With --parent-tree: the setting OFF on this
     tree's library and on another build's (the parent commit's), one child process each,
     alternating, a.rounds times -- the idle cost of the change against its run-to-run spread."""
     import ctypes
@@ -244,7 +263,7 @@ def alternations_leg(a):
                 env = dict(os.environ)
                 if lib:
                     env["YARA_AMD_PACKAGE_ROOT"] = lib
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--alternations",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--" + mode,
                                     "--child", "--gib", str(a.gib), "--reps", str(a.reps)],
                                    env=env, capture_output=True, text=True, timeout=300)
                 if r.returncode != 0:   # (nothing more is started on the device)
@@ -268,52 +287,62 @@ def alternations_leg(a):
     sys.path.append(REPO)   # (oracle; behind a --parent-tree package root)
     import oracle
     import planted
-    n = int(a.gib * (1 << 30))
     golden = os.path.join(REPO, "tests", "golden")
-    host = planted.rx_buffer(oracle.xorshift, n, 19)   # (rx_1M's generator at this size)
     stream = torch.cuda.Stream()
-    buf = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
-    buf[:n] = torch.from_numpy(host).cuda()
-    torch.cuda.synchronize()
-    sc = yara_amd.Scanner(yara_amd.Tables.from_npz(os.path.join(golden, "tables", "rx.npz"),
-                                                   strings=True), stream=stream.cuda_stream)
-    sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
-    sc.scan_device(buf.data_ptr(), n)
-    sc.device_result()
+    inputs = [("rx planted", os.path.join(golden, "tables", "rx.npz"),
+               lambda: planted.rx_buffer(oracle.xorshift, int(a.gib * (1 << 30)), 19))]   # (rx_1M's generator)
+    if mode == "loops" and not a.child:
+        inputs.append(("65536 planted Rn6!a..z records", os.path.join(golden, "loops", "tables.npz"),
+                       lambda: planted_runs(65536)))
+    out = {"reps": a.reps, "classes": "LITERAL | HEX", "runs": []}
+    for name, tables, make in inputs:
+        host = make()
+        n = host.size
+        buf = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
+        buf[:n] = torch.from_numpy(host).cuda()
+        torch.cuda.synchronize()
+        sc = yara_amd.Scanner(yara_amd.Tables.from_npz(tables, strings=True), stream=stream.cuda_stream)
+        sc.set_match_classes(yara_amd.MATCH_LITERAL | yara_amd.MATCH_HEX)
+        sc.scan_device(buf.data_ptr(), n)
+        sc.device_result()
 
-    def stage(on):   # (ms, n_matches, n_rest): the device call alone
-        if on is not None:
-            sc.set_alternations(on)
-        pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
-        nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        _lib.check("yr_amd_match_device", _lib.lib().yr_amd_match_device(
-            sc._h, 0, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr), ctypes.byref(nr)))
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1), nm.value, nr.value
+        def stage(on):   # (ms, n_matches, n_rest): the device call alone
+            if on is not None:
+                getattr(sc, "set_" + mode)(on)
+            pm, pr = ctypes.c_void_p(), ctypes.c_void_p()
+            nm, nr = ctypes.c_uint64(), ctypes.c_uint64()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            _lib.check("yr_amd_match_device", _lib.lib().yr_amd_match_device(
+                sc._h, 0, ctypes.byref(pm), ctypes.byref(nm), ctypes.byref(pr), ctypes.byref(nr)))
+            e1.record(stream)
+            e1.synchronize()
+            return e0.elapsed_time(e1), nm.value, nr.value
 
-    if a.child:   # the setting is never touched: the same calls on either library
-        for _ in range(3):
-            stage(None)
-        print(json.dumps({"off_ms": med([stage(None)[0] for _ in range(a.reps)])}), flush=True)
-        return
-    for _ in range(2):   # warm-up: buffers grown, clocks up
-        stage(False)
-        stage(True)
-    off, on = [], []
-    for _ in range(a.reps):   # interleaved
-        ms, m_off, r_off = stage(False)
-        off.append(ms)
-        ms, m_on, r_on = stage(True)
-        on.append(ms)
-    out = {"bytes": n, "reps": a.reps, "classes": "LITERAL | HEX", "input": "rx planted",
-           "records": sc.verify_device(0)[1],
-           "off": {"matches": m_off, "rest": r_off, "match_device_ms": med(off), "min_max_ms": span(off)},
-           "on": {"matches": m_on, "rest": r_on, "match_device_ms": med(on), "min_max_ms": span(on)},
-           "added_ms": round(med(on) - med(off), 4), "alternation_records": r_off - r_on}
-    print(json.dumps(out), flush=True)
+        if a.child:   # the setting is never touched: the same calls on either library
+            for _ in range(3):
+                stage(None)
+            print(json.dumps({"off_ms": med([stage(None)[0] for _ in range(a.reps)])}), flush=True)
+            return
+        for _ in range(2):   # warm-up: buffers grown, clocks up
+            stage(False)
+            stage(True)
+        off, on = [], []
+        for _ in range(a.reps):   # interleaved
+            ms, m_off, r_off = stage(False)
+            off.append(ms)
+            ms, m_on, r_on = stage(True)
+            on.append(ms)
+        run = {"bytes": n, "input": name, "records": sc.verify_device(0)[1],
+               "off": {"matches": m_off, "rest": r_off, "match_device_ms": med(off), "min_max_ms": span(off)},
+               "on": {"matches": m_on, "rest": r_on, "match_device_ms": med(on), "min_max_ms": span(on)},
+               "added_ms": round(med(on) - med(off), 4), mode[:-1] + "_records": r_off - r_on}
+        out["runs"].append(run)
+        print(json.dumps(run), flush=True)
+        sc.close()
+        del buf
+    if mode == "alternations":   # (one input: the file's shape of before)
+        out = dict(out, **out.pop("runs")[0])
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
@@ -333,15 +362,18 @@ def main():
                          "on planted copies of the hexwide fixture's `back` string")
     ap.add_argument("--alternations", action="store_true",
                     help="alternation strings: the setting off and on, on rx's planted input")
+    ap.add_argument("--loops", action="store_true",
+                    help="loop strings: the setting off and on, on rx's planted input and on "
+                         "planted records of the loops fixture's `run` string")
     ap.add_argument("--parent-tree", default=None,
-                    help="with --alternations: a directory holding another build's yara_amd package "
+                    help="with --alternations or --loops: a directory holding another build's yara_amd package "
                          "(the parent commit's, with its library) to time the setting off against, "
                          "alternating child processes")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    if a.alternations:
-        return alternations_leg(a)
+    if a.alternations or a.loops:
+        return alternations_leg(a, "loops" if a.loops else "alternations")
     if a.hex_wide:
         return hex_wide_leg(a)
     if a.hex:

@@ -50,7 +50,8 @@ several files go through do not have it: their calls stay in the count on stderr
 
 --loops: with --hex or --hex-wide, the loop strings too on the block path
 (yr_amd_scanner_set_loops): text regexps with * and +, /[a-z]+\\.php/, runs up to
-YR_RE_SCAN_LIMIT bytes.  The batches do not have it.
+YR_RE_SCAN_LIMIT bytes.  The batches several files go through settle them too
+(yr_amd_scanner_set_batch_loops), every file's runs inside the file.
 
 --chains: the chained hex strings too (yr_amd_scanner_set_chains): a hex string
 that libyara split at a jump wider than 200 bytes is printed as matches of its
@@ -132,6 +133,7 @@ def main():
     sc.set_chains(chains)
     sc.set_alternations(alternations)
     sc.set_loops(loops)
+    sc.set_batch_loops(loops)
     sc.set_batch_chains(chains)
     paths = argv[1:]
     if len(paths) == 1:

@@ -345,6 +345,7 @@ class Scanner:
         self._alternations = False   # set_alternations
         self._loops = False   # set_loops
         self._batch_alternations = False   # set_batch_alternations
+        self._batch_loops = False   # set_batch_loops
 
     # -- host block: the _yr_scanner_scan_mem_block replacement ---------------
     def candidates(self, data: np.ndarray):
@@ -451,7 +452,7 @@ class Scanner:
         """Settle loop strings too (yr_amd_scanner_set_loops): the strings
         ``Tables.loop_strings`` names, runs up to YR_RE_SCAN_LIMIT bytes.  Read
         only while the classes include MATCH_HEX; the batch calls never read
-        it."""
+        it (theirs is set_batch_loops)."""
         _lib.check("yr_amd_scanner_set_loops",
                    _lib.lib().yr_amd_scanner_set_loops(self._h, int(enable)))
         self._loops = bool(enable)
@@ -544,9 +545,21 @@ class Scanner:
                    _lib.lib().yr_amd_scanner_set_batch_alternations(self._h, int(enable)))
         self._batch_alternations = bool(enable)
 
-    def _with_batch_hex(self, hex, call, wide=False, chains=False, alternations=False):
+    def set_batch_loops(self, enable: bool):
+        """Settle loop strings in the BATCH match stage too
+        (yr_amd_scanner_set_batch_loops): per buffer, what ``set_loops`` gives
+        for that buffer alone, the strings those of ``Tables.loop_strings``.
+        Read only by the batch calls and only while the batch classes include
+        MATCH_HEX; the single-block calls never read it."""
+        _lib.check("yr_amd_scanner_set_batch_loops",
+                   _lib.lib().yr_amd_scanner_set_batch_loops(self._h, int(enable)))
+        self._batch_loops = bool(enable)
+
+    def _with_batch_hex(self, hex, call, wide=False, chains=False, alternations=False, loops=False):
         # _with_hex for the batch calls' settings
         was, was_wide = self._batch_classes, self._batch_hex_wide
+        if not loops or self._batch_loops:
+            loops = False
         if not alternations or self._batch_alternations:
             alternations = False
         if not hex or (was & MATCH_HEX):
@@ -563,9 +576,13 @@ class Scanner:
             self.set_batch_chains(True)
         if alternations:
             self.set_batch_alternations(True)
+        if loops:
+            self.set_batch_loops(True)
         try:
             return call()
         finally:
+            if loops:
+                self.set_batch_loops(False)
             if alternations:
                 self.set_batch_alternations(False)
             if chains:
@@ -776,7 +793,7 @@ class Scanner:
 
     # -- final matches of a batch ------------------------------------------------
     def match_batch_device(self, bases=None, hex: bool = False, wide: bool = False,
-                           chains: bool = False, alternations: bool = False):
+                           chains: bool = False, alternations: bool = False, loops: bool = False):
         """(matches, match_off, rest, rest_off) of the last completed batch scan
         (yr_amd_match_batch_device), copied to the host: buffer k's
         ``matches[match_off[k]:match_off[k + 1]]`` and
@@ -793,9 +810,11 @@ class Scanner:
         ``alternations=True`` settles the alternation strings for this call
         (set_batch_alternations), as ``string_matches(hex=True,
         alternations=True)`` does for the buffer alone; like ``wide`` it goes
-        with the hex class."""
+        with the hex class.  ``loops=True`` does the same for the loop strings
+        (set_batch_loops), as ``string_matches(hex=True, loops=True)`` does
+        for the buffer alone."""
         return self._with_batch_hex(hex, lambda: self._match_batch_device(bases), wide, chains,
-                                    alternations)
+                                    alternations, loops)
 
     def _match_batch_device(self, bases):
         from ._hip import memcpy
@@ -818,14 +837,14 @@ class Scanner:
         return matches, match_off, rest, rest_off
 
     def batch_string_matches(self, buffers, bases=None, hex: bool = False, wide: bool = False,
-                             chains: bool = False, alternations: bool = False):
+                             chains: bool = False, alternations: bool = False, loops: bool = False):
         """(matches, match_off, rest, rest_off) of a list of host buffers
         (yr_amd_scan_batch_matches): buffer k's slices equal
         ``string_matches(buffers[k], bases[k], hex=hex, wide=wide,
-        chains=chains, alternations=alternations)``.  One scan, one
-        pre-verification and one match stage for all of them."""
+        chains=chains, alternations=alternations, loops=loops)``.  One scan,
+        one pre-verification and one match stage for all of them."""
         return self._with_batch_hex(hex, lambda: self._batch_string_matches(buffers, bases), wide,
-                                    chains, alternations)
+                                    chains, alternations, loops)
 
     def _batch_string_matches(self, buffers, bases):
         bufs = [_arr(b, np.uint8).reshape(-1) for b in buffers]
@@ -854,7 +873,7 @@ class Scanner:
 
     def batch_string_matches_device(self, buffers, bases=None, hex: bool = False,
                                     wide: bool = False, chains: bool = False,
-                                    alternations: bool = False):
+                                    alternations: bool = False, loops: bool = False):
         """batch_string_matches for buffers in device memory (see
         batch_candidates_device), through the gather call."""
         ptrs, sizes = _device_buffers(buffers)
@@ -863,7 +882,7 @@ class Scanner:
         self.scan_batch_gather_device(ptrs, sizes)
         self.batch_result()
         return self.match_batch_device(bases, hex=hex, wide=wide, chains=chains,
-                                       alternations=alternations)
+                                       alternations=alternations, loops=loops)
 
     # -- device-resident block (benchmark path) -------------------------------
     def scan_device(self, d_ptr: int, block_size: int, byte_begin: int = 0, byte_end=None):

@@ -181,6 +181,7 @@ PROTOTYPES = {
     "yr_amd_scanner_set_batch_chains": (_int, [_vp, _int]),
     "yr_amd_scanner_batch_chain_waves": (_int, [_vp, _u32p]),
     "yr_amd_scanner_set_batch_alternations": (_int, [_vp, _int]),
+    "yr_amd_scanner_set_batch_loops": (_int, [_vp, _int]),
     "yr_amd_tables_match_strings": (_int, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32]),
 }
 

@@ -545,6 +545,14 @@ hipError_t launch_alt_waves(const AltParams& a, uint32_t waves, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_batch_alt_waves(const BatchAltParams& a, uint32_t waves, hipStream_t s) {
+  const uint64_t n = a.b.w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || a.qcap == 0 || a.b.nbuf == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_alt_measure_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_batch_alt_measure(const BatchAltParams& a, uint32_t waves, hipStream_t s) {
   const HexWideParams& w = a.b.w;
   const uint64_t n = w.h.m.n;

@@ -34,6 +34,11 @@
 // One wave per workgroup: the table is 32 KiB, the class bitmaps 2 KiB, so
 // four waves share a CU's LDS -- and the sweeps are serial chains on the
 // scalar unit, which more waves per SIMD would not hide anyway.
+//
+// The batch calls (yr_amd_scanner_set_batch_loops; matches.h BatchLoopParams,
+// DESIGN.md 18.11) run the same machinery per buffer: the queue holds (record,
+// buffer) pairs, loop_record gets the buffer as its block, and the table is
+// dynamic LDS sized to the batch's largest buffer.
 #include "internal.h"
 #include "matches.h"
 #include "match_measure.h"
@@ -346,22 +351,28 @@ __global__ void loop_clear_kernel(LoopParams l) {
 // queue kernel left of the record -- its key, F, its set {mask, base}, the item
 // count -- which is what the narrow hex path leaves; anything else leaves the
 // record in the rest.
-__device__ void loop_record(const LoopParams& l, uint32_t r, uint32_t* cls, uint64_t* tab) {
-  const HexWideParams& w = l.a.w;
+// The block of both runs is [data, data + size) and `offset` the record's
+// position in it: the scanned block, or -- a batch -- the record's own buffer
+// and its local offset.  loop_byte reads only below max_bytes_matched, so no
+// byte outside the block is read.  tab holds `words` words: a forward run whose
+// last position max_bytes_matched is not inside them leaves the record in the
+// rest before anything is written.
+__device__ void loop_record(const LoopTables& t, const HexWideParams& w, uint32_t r, const uint8_t* data,
+                            uint64_t size, uint64_t offset, uint32_t* cls, uint64_t* tab, uint32_t words) {
   const HexMatchParams& q = w.h;
   const MatchParams& p = q.m;
   const VerifyRec rec = p.recs[r];
-  const AltProg prog = l.t.progs[rec.pool_index];
-  const uint64_t offset = rec.offset;
-  if (prog.n_fwd == 0 || prog.n_fwd > kAltMaxInsns || prog.n_bwd > kAltMaxInsns || offset >= p.size)
+  const AltProg prog = t.progs[rec.pool_index];
+  if (prog.n_fwd == 0 || prog.n_fwd > kAltMaxInsns || prog.n_bwd > kAltMaxInsns || offset >= size)
     return;   // (never: what the measure pass appended)
   const bool dot_all = (p.pool[rec.pool_index].flags & kStrDotAll) != 0;
-  const uint8_t* d = p.data + offset;
+  const uint8_t* d = data + offset;
   LoopProg g;
   HexSet B;
   uint32_t last = 0, F = 0;
-  int maxb = (int)min<uint64_t>(p.size - offset, (uint64_t)kReScanLimit);
-  loop_load(l.t, prog.fwd, prog.n_fwd, cls, g);
+  int maxb = (int)min<uint64_t>(size - offset, (uint64_t)kReScanLimit);
+  if ((uint32_t)maxb >= words) return;   // (never: the host sizes the table to the largest buffer)
+  loop_load(t, prog.fwd, prog.n_fwd, cls, g);
   if (!loop_sweep<true>(g, d, maxb, dot_all, cls, tab, last, B)) return;
   if (!loop_reach(g, d, maxb, dot_all, cls, tab, last)) return;
   if (!loop_walk(g, tab, last, F)) return;   // (no path to MATCH: the host verifies it and finds nothing)
@@ -370,7 +381,7 @@ __device__ void loop_record(const LoopParams& l, uint32_t r, uint32_t* cls, uint
     B = HexSet{1ull, 0u, 0u};
   } else {
     maxb = (int)min<uint64_t>(offset, (uint64_t)kReScanLimit);
-    loop_load(l.t, prog.bwd, prog.n_bwd, cls, g);
+    loop_load(t, prog.bwd, prog.n_bwd, cls, g);
     if (!loop_sweep<false>(g, d, maxb, dot_all, cls, tab, last, B)) return;
     if (B.mask == 0) return;
   }
@@ -392,7 +403,8 @@ __global__ __launch_bounds__(64) void loop_measure_kernel(LoopParams l) {
   for (uint32_t slot = blockIdx.x; slot < n; slot += gridDim.x) {
     const uint32_t r = __builtin_amdgcn_readfirstlane(l.queue[slot]);
     if (r >= l.a.w.h.m.n) continue;   // (never)
-    loop_record(l, r, classes, tab);
+    const MatchParams& p = l.a.w.h.m;
+    loop_record(l.t, l.a.w, r, p.data, p.size, p.recs[r].offset, classes, tab, kLoopPositions);
   }
 }
 
@@ -414,6 +426,173 @@ __global__ __launch_bounds__(256) void loop_unique_kernel(LoopUniqueParams u) {
   uint64_t from = i;
   if (u.str_loop[(uint32_t)(key >> 32)] == (kLoopString | kLoopGreedy))
     while (from + 1 < q.n_items && p.sorted_keys[from + 1] == key) ++from;
+  const uint32_t r = p.sorted_index[from];
+  const MatchMeasure m = p.meas[r];
+  const VerifyRec rec = p.recs[r];
+  MatchRec o;
+  o.offset = key & 0xFFFFFFFFull;
+  o.string = (uint32_t)(key >> 32);
+  o.length = m.length + (uint32_t)((rec.offset & 0xFFFFFFFFull) - o.offset);
+  o.xor_key = m.xor_key;
+  o.pool_index = rec.pool_index;
+  const uint64_t g = i / kGroup;
+  p.out[q.uchunk_off[g / kChunkGroups] + q.ublock_off[g] + lanes_below(mask)] = o;
+}
+
+// ---- The batch's loop strings (matches.h BatchLoopParams) ----
+
+// batch_alt_measure_queue_kernel's twin (alternations.hip) with the third
+// queue, as loop_measure_queue_kernel is alt_measure_queue_kernel's: the
+// record's buffer is searched in rec_off once, here; a record of a loop string
+// inside its buffer is a rest record for now and is appended to the loop queue
+// as the pair (record, buffer); alternation records (alts) and wide records
+// (WIDE) are queued as there.  Every batch buffer is whole -- never a window.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void batch_loop_measure_queue_kernel(BatchLoopParams l) {
+  __shared__ __attribute__((aligned(16))) uint8_t codebuf[256 * kHexCodeBytes + 16];
+  const BatchAltParams& a = l.a;
+  const BatchHexWideParams& b = a.b;
+  const HexWideParams& w = b.w;
+  const MatchParams& p = w.h.m;
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool wide = false, alt = false, loop = false;
+  uint32_t lo = 0;
+  if (r < p.n) {
+    uint32_t hi = b.nbuf;   // rec_off[lo] <= r < rec_off[hi]  (rec_off[nbuf] == n)
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (b.rec_off[mid] <= r) lo = mid; else hi = mid;
+    }
+    HexMatchParams q = w.h;
+    q.m.data = p.data + b.starts[lo];
+    q.m.size = b.sizes[lo];
+    q.m.win_lo = 0;
+    q.m.win_hi = q.m.size;
+    const VerifyRec rec = p.recs[r];
+    const DevPoolRec e = p.pool[rec.pool_index];
+    const uint32_t str = p.pool_string[rec.pool_index];
+    MatchMeasure m;
+    HexSet set{1ull, 0u, 0u};
+    bool is_match;
+    const bool is_loop = l.t.str_loop[str] != 0;
+    if (is_loop || (l.alts != 0 && a.t.str_alt[str] != 0)) {
+      m.length = 0;
+      m.xor_key = 0;
+      is_match = false;
+      const bool in = rec.offset < q.m.size;
+      loop = in && is_loop;
+      alt = in && !is_loop;
+    } else if ((q.classes & kMatchHex) && string_is_final_hex(e.flags)) {
+      m.length = 0;
+      m.xor_key = 0;
+      const uint32_t buf = (uint32_t)(uintptr_t)(codebuf + threadIdx.x * kHexCodeBytes);
+      const int v = measure_hex<WIDE>(q, e, rec.offset, buf, m, set);
+      is_match = v == kHexMatch;
+      wide = WIDE && v == kHexWide;
+      if (!is_match) set = HexSet{1ull, 0u, 0u};
+    } else {
+      is_match = measure(q.m, e, rec.offset, m);
+    }
+    const uint32_t string = is_match ? str : p.n_strings;
+    p.keys[r] = (uint64_t)string << 32 | (rec.offset & 0xFFFFFFFFull);
+    p.meas[r] = m;
+    w.h.sets[r] = set;
+    b.buf[r] = lo;
+    w.icount[r] = is_match ? (uint32_t)__popcll(set.mask) : 0u;
+  }
+  if (WIDE) {
+    const uint64_t qmask = __ballot(wide);
+    if (qmask != 0) {   // (wave-uniform)
+      uint32_t at = 0;
+      if ((threadIdx.x & 63u) == 0) at = atomicAdd(w.qlen, (uint32_t)__popcll(qmask));
+      at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(qmask);
+      if (wide && at < w.qcap) {
+        w.queue[at] = (uint32_t)r;
+        b.qbuf[at] = lo;
+      }
+    }
+  }
+  const uint64_t amask = __ballot(alt);
+  if (amask != 0) {   // (wave-uniform; only with alts)
+    uint32_t at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(a.qlen, (uint32_t)__popcll(amask));
+    at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(amask);
+    if (alt && at < a.qcap) {
+      a.queue[at] = (uint32_t)r;
+      a.qbuf[at] = lo;
+    }
+  }
+  const uint64_t lmask = __ballot(loop);
+  if (lmask != 0) {   // (wave-uniform)
+    uint32_t at = 0;
+    if ((threadIdx.x & 63u) == 0) at = atomicAdd(l.qlen, (uint32_t)__popcll(lmask));
+    at = (uint32_t)__shfl((int)at, 0, 64) + lanes_below(lmask);
+    if (loop && at < l.qcap) {
+      l.queue[at] = (uint32_t)r;
+      l.qbuf[at] = lo;
+    }
+  }
+  // (the per-wave counts are hex_wide_recount_kernel's: they include all queues' results)
+}
+
+__global__ void batch_loop_clear_kernel(BatchLoopParams l) {
+  *l.qlen = 0;
+  if (l.alts != 0) *l.a.qlen = 0;
+}
+
+// loop_measure_kernel for a batch: one WAVE (one workgroup) per queued pair, a
+// fixed grid striding over the queue.  Record and buffer come from the queue
+// entry, the buffer's bounds from starts / sizes through scalar registers.
+// loop_record sees the buffer as the whole block of both runs, so a run reads
+// at most min(sizes[k], YR_RE_SCAN_LIMIT) bytes of it and its positions are 0
+// .. that: the table is the launch's dynamic LDS, l.words = min(largest buffer,
+// YR_RE_SCAN_LIMIT) + 1 words the host sized to the batch -- 32 KiB only where
+// a buffer is 4 KiB or more, a quarter of that for 1 KiB buffers, so that more
+// workgroups share a CU's LDS.  l.words is the hard bound: loop_record leaves a
+// record whose run would pass it in the rest without a write.
+__global__ __launch_bounds__(64) void batch_loop_measure_kernel(BatchLoopParams l) {
+  extern __shared__ uint64_t batch_tab[];   // [l.words]
+  __shared__ uint32_t classes[kAltMaxInsns * kLoopClassWords];
+  const BatchHexWideParams& b = l.a.b;
+  const MatchParams& p = b.w.h.m;
+  const uint32_t len = *l.qlen;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *l.qlen_out = len;
+  const uint32_t n = min(len, l.qcap);
+  for (uint32_t slot = blockIdx.x; slot < n; slot += gridDim.x) {
+    const uint32_t r = __builtin_amdgcn_readfirstlane(l.queue[slot]);
+    const uint32_t k = __builtin_amdgcn_readfirstlane(l.qbuf[slot]);
+    if (r >= p.n || k >= b.nbuf) continue;   // (never: what the measure pass appended)
+    loop_record(l.t, b.w, r, p.data + b.starts[k], b.sizes[k], p.recs[r].offset, classes, batch_tab,
+                l.words);
+  }
+}
+
+// batch_hex_unique_kernel<1> (matches.hip) with replace_if_exists, as
+// loop_unique_kernel: the run of items with one (buffer, string, offset) has
+// one key and one buf[sorted_index[.]] and is in record order (the sort is
+// stable); a greedy loop string takes its last item's record, everything else
+// the first's.  The run ends at another key or another buffer: two buffers
+// with the same bytes at the same local offset never merge.
+__global__ __launch_bounds__(256) void batch_loop_unique_kernel(BatchLoopUniqueParams u) {
+  const BatchHexParams& b = u.b;
+  const HexMatchParams& q = b.h;
+  const MatchParams& p = q.m;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool keep = false;
+  uint64_t key = 0;
+  uint32_t k = 0;
+  if (i < q.n_items) {
+    key = p.sorted_keys[i];
+    k = b.buf[p.sorted_index[i]];
+    keep = (uint32_t)(key >> 32) < p.n_strings &&
+           (i == 0 || p.sorted_keys[i - 1] != key || b.buf[p.sorted_index[i - 1]] != k);
+  }
+  const uint64_t mask = __ballot(keep);
+  if (!keep) return;
+  uint64_t from = i;
+  if (u.str_loop[(uint32_t)(key >> 32)] == (kLoopString | kLoopGreedy))
+    while (from + 1 < q.n_items && p.sorted_keys[from + 1] == key && b.buf[p.sorted_index[from + 1]] == k)
+      ++from;
   const uint32_t r = p.sorted_index[from];
   const MatchMeasure m = p.meas[r];
   const VerifyRec rec = p.recs[r];
@@ -463,6 +642,47 @@ hipError_t launch_loop_measure(const LoopParams& l, uint32_t waves, hipStream_t 
 hipError_t launch_loop_unique(const LoopUniqueParams& u, hipStream_t s) {
   if (u.h.n_items == 0) return hipSuccess;
   hipLaunchKernelGGL(loop_unique_kernel, dim3((uint32_t)((u.h.n_items + 255) / 256)), dim3(256), 0, s, u);
+  return hipGetLastError();
+}
+
+hipError_t launch_batch_loop_measure(const BatchLoopParams& l, uint32_t waves, hipStream_t s) {
+  const BatchAltParams& a = l.a;
+  const HexWideParams& w = a.b.w;
+  const uint64_t n = w.h.m.n;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  if (waves == 0 || l.qcap == 0 || w.qcap == 0 || a.b.nbuf == 0 || (l.alts != 0 && a.qcap == 0) ||
+      l.words < 2 || l.words > kLoopPositions)
+    return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)((n + 255) / 256));
+  // (kernels, not memsets: the stage may be recorded into a graph)
+  hipError_t e = launch_hex_wide_piece(w, waves, 0, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(batch_loop_clear_kernel, dim3(1), dim3(1), 0, s, l);
+  if (a.wide)
+    hipLaunchKernelGGL(batch_loop_measure_queue_kernel<true>, grid, dim3(256), 0, s, l);
+  else
+    hipLaunchKernelGGL(batch_loop_measure_queue_kernel<false>, grid, dim3(256), 0, s, l);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (l.alts != 0) {
+    e = launch_batch_alt_waves(a, waves, s);
+    if (e != hipSuccess) return e;
+  }
+  // (the table: l.words words of dynamic LDS, at most 32 KiB + 8 beside the 2 KiB of bitmaps)
+  hipLaunchKernelGGL(batch_loop_measure_kernel, dim3(waves), dim3(64), l.words * sizeof(uint64_t), s, l);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (a.wide) {
+    e = launch_batch_hex_wide_waves(a.b, waves, s);
+    if (e != hipSuccess) return e;
+  }
+  return launch_hex_wide_piece(w, waves, 2, s);
+}
+
+hipError_t launch_batch_loop_unique(const BatchLoopUniqueParams& u, hipStream_t s) {
+  const uint64_t n = u.b.h.n_items;
+  if (n == 0 || n > kMatchMaxRecords) return n == 0 ? hipSuccess : hipErrorInvalidValue;
+  hipLaunchKernelGGL(batch_loop_unique_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, u);
   return hipGetLastError();
 }
 

@@ -409,6 +409,48 @@ struct LoopUniqueParams {
 };
 hipError_t launch_loop_unique(const LoopUniqueParams& u, hipStream_t s);
 
+// ---- The batch's loop strings (yr_amd_scanner_set_batch_loops) ----
+// BatchAltParams and LoopParams at once.  A queue entry is a pair, as the
+// batch's other queues': the record in queue[slot], its buffer in qbuf[slot];
+// the wave sees the buffer [arena + starts[k], + sizes[k]) as the whole block
+// of both runs.  A run inside a buffer reads at most min(sizes[k],
+// YR_RE_SCAN_LIMIT) bytes, so the wave's table of live sets is `words` =
+// min(largest buffer, YR_RE_SCAN_LIMIT) + 1 words of dynamic LDS, not
+// kLoopPositions; the wave treats `words` as a hard bound.  A settled record
+// leaves {mask, base} as in LoopParams, so the items' CSR (icount / istart),
+// the expansion, the sort and match_off run unchanged.
+// A struct of its own: BatchAltParams and LoopParams are kernel arguments of
+// the kernels above, which stay what they are.  a.b is used either way (as
+// BatchAltParams uses b); a.t / a.queue / a.qbuf / a.qlen only with `alts`.
+struct BatchLoopParams {
+  BatchAltParams a;
+  LoopTables t;
+  uint32_t* queue;              // [qcap] the queued loop records
+  uint32_t* qbuf;               // [qcap] by queue slot: the queued record's buffer
+  uint32_t* qlen;
+  uint32_t qcap;
+  uint64_t* qlen_out;           // qlen for the host (pinned)
+  uint32_t alts;                // alternation strings are settled too
+  uint32_t words;               // the table's words: 2 .. kLoopPositions
+};
+// launch_loop_measure for a batch: all queues cleared, the twin of
+// batch_alt_measure_queue_kernel that queues loop pairs too, one wave per
+// queued alternation pair (alts), per queued loop pair (words * 8 bytes of
+// dynamic LDS each), per wide pair (a.wide), the recount.
+hipError_t launch_batch_loop_measure(const BatchLoopParams& l, uint32_t waves, hipStream_t s);
+// One wave per queued alternation pair on its own (batch_alt_measure_kernel),
+// for that launcher.
+hipError_t launch_batch_alt_waves(const BatchAltParams& a, uint32_t waves, hipStream_t s);
+// launch_batch_hex_unique pass 1 with replace_if_exists, as launch_loop_unique:
+// a run of items with one (buffer, string, offset) is in record order; a greedy
+// loop string takes its last item's record, everything else the first's.
+// (Pass 0 is launch_batch_hex_unique's.)
+struct BatchLoopUniqueParams {
+  BatchHexParams b;
+  const uint8_t* str_loop;
+};
+hipError_t launch_batch_loop_unique(const BatchLoopUniqueParams& u, hipStream_t s);
+
 // ---- Chained strings (yr_amd_scanner_set_chains; chains.hip) ----
 // libyara splits a hex string at every jump wider than
 // YR_STRING_CHAINING_THRESHOLD into a chain S0 <- S1 <- ... (chained_to links

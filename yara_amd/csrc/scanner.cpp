@@ -304,8 +304,11 @@ struct yr_amd_scanner {
   bool batch_alternations = false;
   uint32_t* d_aqueue = nullptr;
   size_t aqueue_cap = 0;
-  // loop strings (yr_amd_scanner_set_loops; matches.h LoopParams): [1 + cap], as d_aqueue
+  // loop strings (yr_amd_scanner_set_loops; matches.h LoopParams): d_lqueue is
+  // laid out as d_aqueue is, [1 + cap] single block, [1 + 2 cap] batch
   bool loops = false;
+  // the batch's own setting (yr_amd_scanner_set_batch_loops; matches.h BatchLoopParams)
+  bool batch_loops = false;
   uint32_t* d_lqueue = nullptr;
   size_t lqueue_cap = 0;
   uint64_t* d_chain_ws = nullptr;
@@ -3158,13 +3161,16 @@ namespace {
 // alts: the records of alternation strings are queued with their buffers and
 // measured one wave each (matches.h BatchAltParams), beside the wide path's
 // queue when that is on -- the same two waits.
+// loops: the same for the records of loop strings (matches.h BatchLoopParams),
+// a third queue of pairs served by the one measure path together with the
+// alternation queue; the unique pass then honours replace_if_exists for them.
 inline uint32_t batch_chain_waves(const yr_amd_tables* t) {
   return 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
 }
 
 int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, uint64_t n,
                            uint32_t nbuf, uint64_t* nm, uint64_t* nr, uint64_t* ni, bool chains,
-                           bool alts) {
+                           bool alts, bool loops) {
   const yr_amd_tables* t = s->tables;
   const size_t groups = verify_groups(n) + 1, chunks = verify_chunks(n) + 1;
   const size_t noff = (size_t)nbuf + 1;
@@ -3251,11 +3257,20 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   const uint32_t wide_waves = 8 * (uint32_t)std::min(std::max(t->num_cus, 1), 256);
   BatchHexWideParams bw{};
   BatchAltParams ba{};
-  uint64_t queued = 0, alt_queued = 0;
+  BatchLoopParams bl{};
+  uint64_t queued = 0, alt_queued = 0, loop_queued = 0;
+  // the largest buffer: the sort key's offset bits below, and -- ahead of the
+  // measure pass with loops only, a batch without items never pays for it --
+  // the loop waves' table: a run inside a buffer sees positions 0 ..
+  // min(size, YR_RE_SCAN_LIMIT)
+  uint64_t largest = 1;
+  if (loops)
+    for (uint64_t z : s->h_bsizes) largest = std::max(largest, z);
   // (the inverse of the layout [1 + 2 qcap]: a capacity that holds the queue reallocates nothing)
   size_t aqcap = std::max<size_t>((s->aqueue_cap > 0 ? s->aqueue_cap - 1 : 0) / 2, 256);
+  size_t lqcap = std::max<size_t>((s->lqueue_cap > 0 ? s->lqueue_cap - 1 : 0) / 2, 256);
   for (size_t qcap = std::max<size_t>((s->wqueue_cap > 0 ? s->wqueue_cap - 1 : 0) / 2, 256);;) {
-    if (wide || alts) {   // (alts alone: the wide queue stays empty, the per-record counts are used)
+    if (wide || alts || loops) {   // (without wide its queue stays empty, the per-record counts are used)
       qcap = std::min<size_t>(qcap, kMatchMaxRecords);
       r = grow_geo(s->d_wqueue, s->wqueue_cap, 1 + 2 * qcap);   // the length, the records, their buffers
       if (!r && wide) r = grow_geo(s->d_wsets, s->wsets_cap, qcap * kWideWords);
@@ -3290,9 +3305,29 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
       ba.qlen_out = s->d_mhsum + 6;
       ba.wide = wide ? 1u : 0u;
     }
+    if (loops) {
+      lqcap = std::min<size_t>(lqcap, kMatchMaxRecords);
+      r = grow_geo(s->d_lqueue, s->lqueue_cap, 1 + 2 * lqcap);   // the length, the records, their buffers
+      if (r) return r;
+      if (!alts) {
+        ba.b = bw;
+        ba.wide = wide ? 1u : 0u;
+      }
+      bl.a = ba;
+      bl.t = t->d_loop;
+      bl.qlen = s->d_lqueue;
+      bl.queue = s->d_lqueue + 1;
+      bl.qbuf = s->d_lqueue + 1 + lqcap;
+      bl.qcap = (uint32_t)lqcap;
+      bl.qlen_out = s->d_mhsum + 7;
+      bl.alts = alts ? 1u : 0u;
+      bl.words = (uint32_t)std::min<uint64_t>(largest, (uint64_t)kReScanLimit) + 1;
+    }
     // measure -> the offsets of the rest and of the items -> the rest, its CSR
     // and the items' CSR; wait
-    if (alts)
+    if (loops)
+      HIP_TRY(launch_batch_loop_measure(bl, wide_waves, s->stream));
+    else if (alts)
       HIP_TRY(launch_batch_alt_measure(ba, wide_waves, s->stream));
     else if (wide)
       HIP_TRY(launch_batch_hex_wide_measure(bw, wide_waves, s->stream));
@@ -3317,7 +3352,7 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
                                  s->stream));
     HIP_TRY(launch_match_rest(m, s->stream));
     HIP_TRY(launch_batch_match_offsets(rp, 0, s->stream));
-    if (wide || alts)
+    if (wide || alts || loops)
       HIP_TRY(launch_batch_hex_wide_offsets(bw, s->stream));
     else
       HIP_TRY(launch_batch_hex_offsets(b, 0, s->stream));
@@ -3331,18 +3366,21 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
     HIP_TRY(hipStreamSynchronize(s->stream));
     queued = wide ? s->h_msum[4] : 0;
     alt_queued = alts ? s->h_msum[6] : 0;
-    if (queued > n || alt_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
+    loop_queued = loops ? s->h_msum[7] : 0;
+    if (queued > n || alt_queued > n || loop_queued > n) return YR_AMD_INTERNAL_FATAL_ERROR;
     // a queue that overflowed grows to what was appended, and the pass runs again
     const bool wide_over = wide && queued > bw.w.qcap, alt_over = alts && alt_queued > ba.qcap;
-    if (!wide_over && !alt_over) break;
+    const bool loop_over = loops && loop_queued > bl.qcap;
+    if (!wide_over && !alt_over && !loop_over) break;
     if (wide_over) qcap = std::max<size_t>(queued, 2 * qcap);
     if (alt_over) aqcap = std::max<size_t>(alt_queued, 2 * aqcap);
+    if (loop_over) lqcap = std::max<size_t>(loop_queued, 2 * lqcap);
   }
   *nr = s->h_msum[0];
   const uint64_t hex_items = s->h_msum[3];
   *nm = 0;
   // (a record of the wave-wide path is up to YR_RE_SCAN_LIMIT + 1 items, an
-  // alternation record at most 64)
+  // alternation or loop record at most 64)
   if (*nr > n || hex_items > (wide ? (uint64_t)kReScanLimit + 1 : 64) * (n - *nr) ||
       s->h_mrest_off[nbuf] != *nr)
     return YR_AMD_INTERNAL_FATAL_ERROR;
@@ -3357,6 +3395,9 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   if (debug_level() >= 1 && alts)
     fprintf(stderr, "- %llu verify calls, %llu queued as alternation records // yr_amd_match_batch_device()\n",
             (unsigned long long)n, (unsigned long long)alt_queued);
+  if (debug_level() >= 1 && loops)
+    fprintf(stderr, "- %llu verify calls, %llu queued as loop records // yr_amd_match_batch_device()\n",
+            (unsigned long long)n, (unsigned long long)loop_queued);
   if (items > kMatchMaxRecords) return YR_AMD_INVALID_ARGUMENT;
   if (items == 0) return YR_AMD_SUCCESS;
   r = ensure_match_workspace(s, items);
@@ -3369,8 +3410,8 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   m.out = s->d_mout;
   // the key's bits that vary: the local offsets' (below the largest buffer's
   // size; offset - B only decreases), and the string field's
-  uint64_t largest = 1;
-  for (uint64_t z : s->h_bsizes) largest = std::max(largest, z);
+  if (!loops)
+    for (uint64_t z : s->h_bsizes) largest = std::max(largest, z);
   int lo_bits = 1, hi_bits = 1;
   while (lo_bits < 32 && ((largest - 1) >> lo_bits) != 0) ++lo_bits;
   while (hi_bits < 32 && (m.n_strings >> hi_bits) != 0) ++hi_bits;
@@ -3378,7 +3419,7 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   uint32_t* const index[2] = {s->d_mindex, s->d_mindex + s->match_cap};
   // expand; sort by (buffer, string, offset); distinct (buffer, key) -> their
   // offsets -> the matches and their CSR; wait
-  if (wide || alts) {
+  if (wide || alts || loops) {
     bw.w.h = b.h;
     HIP_TRY(launch_hex_wide_expand(bw.w, wide_waves, s->stream));
   } else {
@@ -3401,7 +3442,10 @@ int match_batch_device_hex(yr_amd_scanner* s, const yr_amd_verify_rec* d_rec, ui
   HIP_TRY(launch_batch_hex_unique(b, 0, s->stream));
   HIP_TRY(launch_block_offsets(b.h.ublock_off, b.h.uchunk_off, items, s->d_mhsum + 1, nullptr, none,
                                s->stream));
-  HIP_TRY(launch_batch_hex_unique(b, 1, s->stream));
+  if (loops)   // (a greedy loop string's last record in its buffer supplies the length: scan.c:756)
+    HIP_TRY(launch_batch_loop_unique(BatchLoopUniqueParams{b, t->d_loop.str_loop}, s->stream));
+  else
+    HIP_TRY(launch_batch_hex_unique(b, 1, s->stream));
   HIP_TRY(launch_batch_hex_offsets(b, 1, s->stream));
   HIP_TRY(hipMemcpyAsync(s->h_match_off.data(), b.match_off, noff * sizeof(uint64_t),
                          hipMemcpyDeviceToHost, s->stream));
@@ -3439,6 +3483,12 @@ int yr_amd_scanner_set_batch_alternations(yr_amd_scanner* s, int enable) {
   return YR_AMD_SUCCESS;
 }
 
+int yr_amd_scanner_set_batch_loops(yr_amd_scanner* s, int enable) {
+  if (s == nullptr || (enable != 0 && enable != 1)) return YR_AMD_INVALID_ARGUMENT;
+  s->batch_loops = enable != 0;
+  return YR_AMD_SUCCESS;
+}
+
 int yr_amd_scanner_batch_chain_waves(const yr_amd_scanner* s, uint32_t* waves) {
   if (s == nullptr || waves == nullptr) return YR_AMD_INVALID_ARGUMENT;
   *waves = batch_chain_waves(s->tables);
@@ -3462,6 +3512,8 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   // alternation strings (yr_amd_scanner_set_batch_alternations): with the hex
   // class only, whose refusal above covers tables without programs
   const bool alts = hex && s->batch_alternations && t->n_alt_strings > 0;
+  // loop strings (yr_amd_scanner_set_batch_loops): the same
+  const bool loops = hex && s->batch_loops && t->n_loop_strings > 0;
   const yr_amd_verify_rec* d_rec = nullptr;
   const uint64_t* rec_off = nullptr;
   int r = yr_amd_verify_batch_device(s, bases, &d_rec, &rec_off);
@@ -3473,7 +3525,7 @@ int yr_amd_match_batch_device(yr_amd_scanner* s, const uint64_t* bases,
   s->h_mrest_off.assign((size_t)nbuf + 1, 0);
   uint64_t nm = 0, nr = 0, ni = 0;
   if (n > 0 && (hex || chains)) {
-    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni, chains, alts);
+    r = match_batch_device_hex(s, d_rec, n, nbuf, &nm, &nr, &ni, chains, alts, loops);
     if (r) return r;
   } else if (n > 0) {   // (no records: no kernel is launched)
     r = ensure_match_workspace(s, n, nbuf);
@@ -3562,7 +3614,7 @@ int yr_amd_scan_batch_matches(yr_amd_scanner* s, const uint8_t* const* data, con
                               const uint64_t** match_off, const yr_amd_verify_rec** rest,
                               const uint64_t** rest_off) {
   if (s == nullptr || s->tables->profile) return YR_AMD_INVALID_ARGUMENT;   // (before any copy)
-  // (yr_amd_scanner_set_batch_alternations too: it is read with the hex class only)
+  // (yr_amd_scanner_set_batch_alternations and _loops too: they are read with the hex class only)
   if ((s->batch_match_classes & kMatchHex) && s->tables->d_re_code == nullptr)
     return YR_AMD_INVALID_ARGUMENT;
   if (s->batch_chains && !s->tables->has_chains) return YR_AMD_INVALID_ARGUMENT;
